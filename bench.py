@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the Harmony iteration engine on MI355X.
 
-    python bench.py --gpus 1 --steps K --warmup W            (defaults finish in ~2-3 minutes)
+    python bench.py --gpus 1 --steps K --warmup W            (set-up, warm-up and the timed steps only)
+    python bench.py --full ...                               (and the diagnostics below: ~2-3 minutes at the defaults)
     python bench.py --gpus N ...                             (launches its own N ranks, one per GPU, over RCCL)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W   (the driver's form)
 
@@ -17,16 +18,25 @@ Workload at --gpus 1: BASELINE.json configs[2] (C3, the roofline point): synthet
 50 PCs, 8 batches, K=100.  `--config c2` selects configs[1] (69k x 50, 4 batches, K=30).
 With N > 1 ranks the default is the job BASELINE.json names for several GPUs: configs[3], 10M cells x 50 PCs,
 16 batches, K=100, cells sharded evenly over the N ranks (STRONG scaling: 10M / N cells per GPU; its one-GPU point
-is the `configs_3_on_one_gpu` entry of the default line); `--config c5` shards configs[4] (10M x 200 PCs, K=200) the
+is the `configs_3_on_one_gpu` entry of the `--full` line); `--config c5` shards configs[4] (10M x 200 PCs, K=200) the
 same way, `--config c3` keeps 1M cells per GPU (weak scaling).  A run that cannot bring up N ranks on N devices
 exits non-zero instead of reporting fewer GPUs.
 
-One JSON line on stdout (rank 0).  Besides the contract fields:
+One JSON line on stdout (rank 0).  A plain run sets up, warms up, times `--steps` steps and prints the contract
+fields (metric, value, unit, higher_is_better, dtype, ms_per_step) with the run's configuration.  `--full` adds
+everything else, each measured outside the timed steps' figure:
   roofline     -- the dominant kernel (k_round, one persistent launch per update_R sweep):
                   algorithmic bytes per launch (cells x (4d + 4K + 4)) / average
-                  launch time from HIP events on the engine's stream, against 8 TB/s HBM.
+                  launch time from HIP events on the engine's stream, against 8 TB/s HBM
+                  (one extra untimed step brackets every kernel family; the timed steps bracket
+                  every 4th launch of the dominant kernel).
+  convergence, lisi, configs_* -- a default run to convergence on the same cells, the LISI of the
+                  embedding before / after it, and the other BASELINE configurations.
   cpu_baseline -- the NumPy oracle (a port of the reference's torch-CPU path) timed on this
                   box's host cores on a bounded sample of the same workload.
+
+`--dump-outputs DIR` writes what the last timed step left for a caller (rank 0's cells) as DIR/<name>.npy:
+Z_corr and R on a fixed, seeded sample of rows (at most 64 MB in all), Y, O, E and the step's objective histories.
 """
 from __future__ import annotations
 
@@ -438,6 +448,36 @@ def side_config_fresh_process(name, rounds, steps, warmup, repeats):
         return out
 
 
+DUMP_BYTES = 56 << 20     # Z_corr and R rows of --dump-outputs; Y, O, E and the histories add well under 1 MB at every config
+DUMP_MAX_ROWS = 65_536
+
+
+def dump_outputs(ho, out_dir):
+    """What the last step left for a caller of run_harmony / Harmony, as float32 / float64 .npy files: Z_corr and R on
+    the same seeded sample of cells in every run (sorted cell ids), Y, O, E, and the objective entries the step appended."""
+    from harmonypy_amd import _capi
+    os.makedirs(out_dir, exist_ok=True)
+    N, d, K = ho.N, ho.d, ho.K
+    n = min(N, DUMP_MAX_ROWS, DUMP_BYTES // (4 * (d + K)))
+    rows = np.sort(np.random.default_rng(0).choice(N, size=n, replace=False))
+    pos = ho._rank[rows]                                       # caller's cell -> the engine's row
+    r = ho.kmeans_rounds[-1]                                   # objective entries appended by the last step
+    arrays = {
+        "Z_corr_sample": ho._engine.get_rows(_capi.HMX_Z_CORR, pos),
+        "R_sample": ho._engine.get_rows(_capi.HMX_R, pos),
+        "Y": ho.Y, "O": ho.O, "E": ho.E,
+        "objective_kmeans": np.asarray(ho.objective_kmeans[-r:], np.float64),
+        "objective_kmeans_dist": np.asarray(ho.objective_kmeans_dist[-r:], np.float64),
+        "objective_kmeans_entropy": np.asarray(ho.objective_kmeans_entropy[-r:], np.float64),
+        "objective_kmeans_cross": np.asarray(ho.objective_kmeans_cross[-r:], np.float64),
+        "objective_harmony": np.asarray(ho.objective_harmony[-1:], np.float64),
+    }
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -454,9 +494,16 @@ def main():
     ap.add_argument("--no-convergence", action="store_true", help="skip the untimed end-to-end run to convergence")
     ap.add_argument("--side", default=None, choices=sorted(CONFIGS), help="print only the side entry of that configuration (one JSON line)")
     ap.add_argument("--side-repeats", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the diagnostics: per-kernel times and roofline, the run to convergence and its LISI, "
+                         "the side configurations and the CPU baseline (default: the timed steps and the result line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.side:
         os.environ["HMX_UPDATE_ORDER"] = "device"
@@ -541,7 +588,7 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    timing = not args.no_roofline
+    timing = args.full and not args.no_roofline
     ktimes_all = {}
     if timing:
         # every family, one untimed step: the per-family kernel milliseconds of the line (diagnosis).  Bracketing all
@@ -580,8 +627,10 @@ def main():
     # ---- second figure of BASELINE.json's metric: wall-clock to convergence of a default run_harmony on the
     #      same cells (its own initialisation: k-means++ seeds on a subsample + Lloyd iterations on the GPU,
     #      natural round / iteration counts), outside the timed region of `value`
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ho, args.dump_outputs)
     conv = None
-    if not args.no_convergence:
+    if args.full and not args.no_convergence:
         del ho
         fence_t = time.perf_counter()
         ho2 = H.run_harmony(Z, meta, ["batch"], nclust=K, max_iter_harmony=0, verbose=False, random_state=0,
@@ -678,7 +727,7 @@ def main():
         out["lisi"] = {"cells": int(len(take)), "pcs": d, "perplexity": 30, "seconds": t_l, "cells_per_sec": len(take) / t_l,
                        "batches": B, "batch_lisi_before": float(before.mean()), "batch_lisi_after": float(after.mean()),
                        "note": "host float64 input to host output, exact neighbours; not part of `value`"}
-    if world == 1 and config == "c3" and not args.no_convergence:
+    if args.full and world == 1 and config == "c3" and not args.no_convergence:
         # BASELINE configs[1] (69k cells x 50 PCs, 4 batches, K=30) measured the same way, for reference: it is
         # latency-bound (its working set lives in the L3; 20 sequential hand-offs per round), so the headline
         # figure is quoted on configs[2], the roofline point
@@ -692,7 +741,7 @@ def main():
         out["configs_3_half_on_one_gpu"] = side_config("c4x2", args.rounds, steps=3, warmup=1, device=f"cuda:{local_rank}")
         # (a process of its own, median of three regions: behind the 10 M-cell entries of this process the same build read 55.6-59.4 M)
         out["configs_4_shard"] = side_config_fresh_process("c5", args.rounds, steps=2, warmup=1, repeats=3)
-    if args.cpu_sample > 0 and world == 1:
+    if args.full and args.cpu_sample > 0 and world == 1:
         out["cpu_baseline"] = cpu_baseline(d, B, K, args.rounds, min(args.cpu_sample, N))
         # the survey's own measurement of the reference at the HEADLINE size (the CPU path is super-linear in N: the sample
         # above flatters it): context beside the in-run figure, never a target

@@ -1,17 +1,17 @@
 #!/bin/bash
 # persistent wide sweep x list prefetch on the side stream: where does the list build of the next round go?
 export TMPDIR=/tmp
-mkdir -p gpurun_out
+mkdir -p bench_out
 run() {
   local label=$1; shift
-  env "$@" timeout 300 python bench.py --config c5 --steps 3 --warmup 1 --cpu-sample 0 --no-convergence --no-lisi > gpurun_out/w.json 2> gpurun_out/w.err
+  env "$@" timeout 300 python bench.py --full --config c5 --steps 3 --warmup 1 --cpu-sample 0 --no-convergence --no-lisi > bench_out/w.json 2> bench_out/w.err
   python - "$label" <<'PY'
 import json, sys
 try:
-    d = json.loads(open("gpurun_out/w.json").read().splitlines()[0])
+    d = json.loads(open("bench_out/w.json").read().splitlines()[0])
     print(sys.argv[1], round(d["value"] / 1e6, 2), "M", round(d["ms_per_step"], 3), "ms", d.get("kernel_ms_per_step"))
 except Exception as ex:
-    print(sys.argv[1], "FAILED", ex, open("gpurun_out/w.err").read()[-1500:])
+    print(sys.argv[1], "FAILED", ex, open("bench_out/w.err").read()[-1500:])
 PY
 }
 {
@@ -28,4 +28,4 @@ import csv, glob
 f = glob.glob('/tmp/prof_ws/**/ws_kernel_stats.csv', recursive=True)
 for row in list(csv.reader(open(f[0])))[:22]: print(row[:6])
 PY
-} 2>&1 | tee gpurun_out/r6_wsweep2.txt
+} 2>&1 | tee bench_out/r6_wsweep2.txt
