@@ -23,8 +23,9 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libhmx.so")
 OBJ_DIR = os.path.join(ROOT, "build", "obj")
-SOURCES = ["hmx_kernels.hip", "hmx_rtz3.hip", "hmx_lisi.hip", "hmx_capi.cpp"]
-HEADERS = [os.path.join(CSRC, "hmx_internal.h"), os.path.join(CSRC, "hmx_device.h"), os.path.join(ROOT, "include", "hmx.h")]
+SOURCES = ["hmx_kernels.hip", "hmx_rtz3.hip", "hmx_lisi.hip", "hmx_io.hip", "hmx_capi.cpp"]
+PUBLIC_HEADERS = [os.path.join(ROOT, "include", "hmx.h"), os.path.join(ROOT, "include", "hmx_device_io.h")]
+HEADERS = [os.path.join(CSRC, "hmx_internal.h"), os.path.join(CSRC, "hmx_device.h")] + PUBLIC_HEADERS
 BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function"]
 
 
@@ -40,10 +41,10 @@ def sources(extra_flags=()) -> list:
 
 
 def build_id(extra_flags=()) -> str:
-    """Hash of everything that decides the kernels: csrc/*, include/hmx.h, the flags."""
+    """Hash of everything that decides the kernels: csrc/*, the public headers, the flags."""
     h = hashlib.sha256()
     files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".cpp", ".h")))
-    for p in files + [os.path.join(ROOT, "include", "hmx.h")]:
+    for p in files + PUBLIC_HEADERS:
         h.update(os.path.basename(p).encode())
         with open(p, "rb") as f:
             h.update(f.read())

@@ -1,4 +1,4 @@
-"""ctypes binding of libhmx.so (include/hmx.h).  Thin: argument marshalling and error text only.
+"""ctypes binding of libhmx.so (include/hmx.h, include/hmx_device_io.h).  Thin: argument marshalling and error text only.
 
 The library is the product's compute path; there is no fallback.  Importing this module
 without a built ``libhmx.so`` raises, and every entry point raises ``HmxError`` with the
@@ -21,6 +21,7 @@ HMX_Z_ORIG, HMX_Z_COS, HMX_Z_CORR, HMX_R, HMX_Y, HMX_O_GROUP, HMX_T_MASS, HMX_W 
 HMX_ROUND_BLOCK_START, HMX_ROUND_CELLS, HMX_ROUND_TILE_GROUP = 8, 9, 10
 HMX_ROUND_CENTROIDS, HMX_ROUND_UPDATE_R, HMX_ROUND_OBJECTIVE = 1, 2, 4
 HMX_ROUND_ALL = 7
+HMX_DTYPE_F32, HMX_DTYPE_F16, HMX_DTYPE_BF16, HMX_DTYPE_F64 = range(4)   # element types of hmx_upload_device
 
 EXPORTS = [
     "hmx_last_error", "hmx_abi_version", "hmx_create", "hmx_destroy", "hmx_upload", "hmx_init_cluster",
@@ -28,6 +29,8 @@ EXPORTS = [
     "hmx_kernel_times", "hmx_enable_timing", "hmx_counters", "hmx_comm_unique_id", "hmx_comm_init", "hmx_set_host_allreduce",
     "hmx_build_id", "hmx_cluster", "hmx_set_timing_stride", "hmx_set_timing_families", "hmx_kmeans_lloyd", "hmx_can_lloyd", "hmx_kmeans_seed", "hmx_compute_lisi", "hmx_get_rows", "hmx_set_ranks", "hmx_peer_export", "hmx_peer_attach", "hmx_peer_selftest", "hmx_peer_enable",
 ]
+# include/hmx_device_io.h: the device I/O path (same ABI version; its own header, see there)
+DEVICE_IO_EXPORTS = ["hmx_upload_device", "hmx_copy_out_device"]
 HMX_PEER_HANDLE_BYTES = 64
 HMX_ABI_VERSION = 8
 HMX_UNIQUE_ID_BYTES = 128
@@ -74,6 +77,8 @@ def load():
     lib.hmx_destroy.argtypes = [vp]
     lib.hmx_destroy.restype = None
     lib.hmx_upload.argtypes = [vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.hmx_upload_device.argtypes = [vp, vp, C.c_int, i64, i64, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.hmx_copy_out_device.argtypes = [vp, C.c_int, vp, i64, i64, vp]
     lib.hmx_kmeans_seed.argtypes = [vp, vp, i64, C.c_uint64, vp, vp]
     lib.hmx_compute_lisi.argtypes = [i32, vp, i64, i32, vp, i32, C.c_double, vp, vp, vp]
     lib.hmx_comm_unique_id.argtypes = [vp]
@@ -102,7 +107,7 @@ def load():
     lib.hmx_enable_timing.argtypes = [vp, C.c_int]
     lib.hmx_set_timing_stride.argtypes = [vp, C.c_int]
     lib.hmx_set_timing_families.argtypes = [vp, C.c_uint]
-    for name in EXPORTS:
+    for name in EXPORTS + DEVICE_IO_EXPORTS:
         if name not in ("hmx_last_error", "hmx_destroy", "hmx_build_id"):
             getattr(lib, name).restype = C.c_int
     lib.hmx_build_id.restype = C.c_char_p
@@ -173,6 +178,28 @@ class Engine:
         _check(self._lib.hmx_upload(self._h, _ptr(Z), _ptr(sc), sc.size, _ptr(tg), tg.size, _ptr(gc),
                                     _ptr(_c(Pr_b, np.float32)), _ptr(_c(theta, np.float32)),
                                     _ptr(_c(sigma, np.float32)), _ptr(lamb), _ptr(global_id), _ptr(source_row)))
+
+    def upload_device(self, ptr, dtype, stride_cell, stride_pc, stream, static_cells, static_tile_group, group_cols, Pr_b,
+                      theta, sigma, lamb, global_id=None, source_row=None):
+        """``upload`` with Z in device memory of the engine's GPU: ``ptr`` its address, cell (n, feature f) at element
+        ``n * stride_cell + f * stride_pc`` of type ``dtype`` (HMX_DTYPE_*); ``stream`` the caller's hipStream_t (int).
+        The caller keeps the memory alive for the call; the library returns once it has read it."""
+        global_id = None if global_id is None else _c(global_id, np.int32)
+        source_row = None if source_row is None else _c(source_row, np.int32)
+        sc = _c(static_cells, np.int32)
+        tg = _c(static_tile_group, np.int32)
+        gc = _c(group_cols, np.int32)
+        lamb = None if lamb is None else _c(lamb, np.float32)
+        _check(self._lib.hmx_upload_device(self._h, C.c_void_p(int(ptr)), int(dtype), int(stride_cell), int(stride_pc),
+                                           C.c_void_p(int(stream) or None), _ptr(sc), sc.size, _ptr(tg), tg.size, _ptr(gc),
+                                           _ptr(_c(Pr_b, np.float32)), _ptr(_c(theta, np.float32)),
+                                           _ptr(_c(sigma, np.float32)), _ptr(lamb), _ptr(global_id), _ptr(source_row)))
+
+    def copy_out_device(self, which, ptr, stride_cell, stride_col, stream):
+        """An N-sized float array (HMX_Z_ORIG / Z_COS / Z_CORR / R) into device memory at ``ptr`` in the caller's cell
+        order, element (cell n, column c) at ``n * stride_cell + c * stride_col``; ordered on ``stream`` (int)."""
+        _check(self._lib.hmx_copy_out_device(self._h, int(which), C.c_void_p(int(ptr)), int(stride_cell), int(stride_col),
+                                             C.c_void_p(int(stream) or None)))
 
     # ---- transports of a sharded job (include/hmx.h) ------------------------------------------
     def comm_init(self, unique_id: bytes, n_ranks: int, rank: int):

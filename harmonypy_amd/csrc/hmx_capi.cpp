@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "hmx.h"
+#include "hmx_device_io.h"
 #include "hmx_internal.h"
 #ifdef RTZ_PROF
 void rtz_prof_dump();
@@ -97,6 +98,11 @@ struct hmx_engine {
     uint64_t pre_seed = 0, pre_counter = 0;
     int64_t pre_cpb = 0;
     DevBuf<int> gstart, chunk_tab, run_count, run_start, global_id;
+    // cell map of the upload (internal row -> caller row; released = identity) and, built on first use by a transfer with
+    // cell stride 1, its inverse; kept for hmx_copy_out_device.  map_perm: the map is a permutation of [0, N)
+    DevBuf<int> cell_map, cell_inv;
+    bool map_perm = true, inv_valid = false;
+    hipEvent_t io_ev[2] = {nullptr, nullptr};   // hand-offs between a caller's stream and the engine's (device I/O path)
     uint64_t seeded_rounds = 0;
     int64_t Ng = 0;              // cells of the whole job (all ranks)
     DevBuf<double> Ogrp, Tmass, Ohist, scratch;
@@ -501,6 +507,8 @@ void hmx_destroy(hmx_engine* e) {
     e->tile_blk[0].release(); e->tile_blk[1].release(); e->tile_blk_zero.release(); e->Osave.release(); e->Opriv.release(); e->Wf.release(); e->Yf.release(); e->Zcf.release();
     e->task_grp.release(); e->gstart.release(); e->chunk_tab.release(); e->run_count.release(); e->run_start.release();
     e->Ogrp.release(); e->Tmass.release(); e->Ohist.release(); e->xch.release(); e->scratch.release();
+    e->cell_map.release(); e->cell_inv.release();
+    for (auto ev : e->io_ev) if (ev) (void)hipEventDestroy(ev);
     e->global_id.release(); e->wait_stats.release(); e->sync_words.p = nullptr; e->sync_words.n = 0; e->Sslots.release(); e->km_hn.release(); e->km_sums.release();
     if (e->sync_host) (void)hipHostFree(e->sync_host);
     comm_release(e);
@@ -513,11 +521,41 @@ void hmx_destroy(hmx_engine* e) {
     delete e;
 }
 
-int hmx_upload(hmx_engine* e, const float* Z, const int32_t* static_cells, int64_t n_static_pos,
-               const int32_t* static_tile_group, int32_t n_static_tiles, const int32_t* group_cols, const float* Pr_b,
-               const float* theta, const float* sigma, const float* lamb, const int32_t* global_id,
-               const int32_t* source_row) {
-    if (!e || !Z || !static_cells || !static_tile_group || !group_cols || !Pr_b || !theta || !sigma)
+namespace {
+
+// Where hmx_upload's Z comes from: host memory (N x d fp32, row-major) or a caller's device tensor.
+struct ZSource {
+    const float* host = nullptr;
+    const void* dev = nullptr;
+    int dtype = HMX_DTYPE_F32;
+    int64_t s_cell = 0, s_pc = 0;
+    hipStream_t caller = nullptr;
+};
+
+int io_events(hmx_engine* e) {
+    for (auto& ev : e->io_ev)
+        if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    return 0;
+}
+
+// the inverse cell map (caller row -> internal row) on the engine's stream; nothing to do for the identity
+int ensure_inverse(hmx_engine* e) {
+    if (!e->cell_map.p || e->inv_valid) return 0;
+    int rc;
+    if ((rc = e->cell_inv.reserve(e->N))) return rc;
+    launch_io_invert(e->cell_map.p, e->cell_inv.p, e->N, e->stream);
+    e->inv_valid = true;
+    return 0;
+}
+
+// the inverse map to hand to the slab kernels: null (identity) unless the upload had a cell map and its inverse is built
+const int* cell_inverse(const hmx_engine* e) { return e->cell_map.p && e->inv_valid ? e->cell_inv.p : nullptr; }
+
+int upload_impl(hmx_engine* e, const ZSource& z, const int32_t* static_cells, int64_t n_static_pos,
+                const int32_t* static_tile_group, int32_t n_static_tiles, const int32_t* group_cols, const float* Pr_b,
+                const float* theta, const float* sigma, const float* lamb, const int32_t* global_id,
+                const int32_t* source_row) {
+    if (!e || !(z.host || z.dev) || !static_cells || !static_tile_group || !group_cols || !Pr_b || !theta || !sigma)
         return fail(HMX_ERR_ARG, "null argument");
     if (!e->cfg.lambda_estimation && !lamb) return fail(HMX_ERR_ARG, "lamb is required unless lambda_estimation");
     if (n_static_pos != (int64_t)n_static_tiles * HMX_TILE) return fail(HMX_ERR_ARG, "n_static_pos must be 16*n_static_tiles");
@@ -546,23 +584,43 @@ int hmx_upload(hmx_engine* e, const float* Z, const int32_t* static_cells, int64
     } else {
         e->global_id.release();
     }
-    if (source_row)
-        for (int64_t i = 0; i < e->N; ++i)
+    bool perm = true;
+    if (source_row) {
+        std::vector<unsigned char> seen(e->N, 0);
+        for (int64_t i = 0; i < e->N; ++i) {
             if (source_row[i] < 0 || source_row[i] >= e->N) return fail(HMX_ERR_ARG, "source_row[%lld] out of range", (long long)i);
-    // Z travels as it is (N x d); the device pads the rows to dp and, with source_row, brings them
-    // into the group-sorted order.  Z_corr's storage is the landing area (N x d <= N x dp floats).
-    {
-        DevBuf<int> srow;
-        if (source_row) {
-            if ((rc = srow.reserve(e->N))) return rc;
-            HIP_TRY(hipMemcpyAsync(srow.p, source_row, e->N * sizeof(int), hipMemcpyHostToDevice, e->stream));
+            perm = perm && !seen[source_row[i]];
+            seen[source_row[i]] = 1;
         }
-        HIP_TRY(hipMemcpyAsync(e->Zcorr.p, Z, (size_t)e->N * e->d * sizeof(float), hipMemcpyHostToDevice, e->stream));
-        launch_load_rows(e->Zcorr.p, e->d, srow.p, e->Zorig.p, e->dp, e->N, e->stream);
-        HIP_TRY(hipMemcpyAsync(e->Zcorr.p, e->Zorig.p, (size_t)e->N * e->dp * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        srow.release();
     }
+    if (z.dev && !perm) return fail(HMX_ERR_ARG, "hmx_upload_device: source_row must be a permutation of the cells");
+    // the cell map stays resident for hmx_copy_out_device
+    if (source_row) {
+        if ((rc = e->cell_map.reserve(e->N))) return rc;
+        HIP_TRY(hipMemcpyAsync(e->cell_map.p, source_row, e->N * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    } else {
+        e->cell_map.release();
+    }
+    e->cell_inv.release();      // the inverse of an earlier upload's map; rebuilt on demand (ensure_inverse)
+    e->map_perm = perm;
+    e->inv_valid = false;
+    if (z.host) {
+        // Z travels as it is (N x d); the device pads the rows to dp and, with source_row, brings them
+        // into the group-sorted order.  Z_corr's storage is the landing area (N x d <= N x dp floats).
+        HIP_TRY(hipMemcpyAsync(e->Zcorr.p, z.host, (size_t)e->N * e->d * sizeof(float), hipMemcpyHostToDevice, e->stream));
+        launch_load_rows(e->Zcorr.p, e->d, e->cell_map.p, e->Zorig.p, e->dp, e->N, e->stream);
+    } else {
+        // the caller's tensor is read where it lies, in its dtype and strides, once the work queued before it on the
+        // caller's stream (whatever produced it) has run; the rows land padded and group-sorted as above
+        if ((rc = io_events(e))) return rc;
+        HIP_TRY(hipEventRecord(e->io_ev[0], z.caller));
+        HIP_TRY(hipStreamWaitEvent(e->stream, e->io_ev[0], 0));
+        if (io_uses_slab(z.s_cell, z.s_pc) && (rc = ensure_inverse(e))) return rc;
+        if (launch_io_load(z.dev, z.dtype, z.s_cell, z.s_pc, e->cell_map.p, cell_inverse(e), e->Zorig.p, e->d, e->dp, e->N, e->stream))
+            return fail(HMX_ERR_ARG, "hmx_upload_device: unknown dtype %d", z.dtype);
+    }
+    HIP_TRY(hipMemcpyAsync(e->Zcorr.p, e->Zorig.p, (size_t)e->N * e->dp * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));   // (device input: the caller may free or overwrite Z once this returns)
     launch_normalize_rows(e->Zorig.p, e->Zcos.p, e->N, e->dp, e->stream);  // harmony.py:238
     e->zcf_valid = false;
     std::vector<float> sg(e->K16, 0.f);
@@ -708,6 +766,40 @@ int hmx_upload(hmx_engine* e, const float* Z, const int32_t* static_cells, int64
     HIP_TRY(hipGetLastError());
     e->uploaded = true;
     return HMX_OK;
+}
+
+}  // namespace
+
+// harmony.py:234-238 (Z_corr / Z_orig built from the host array, Z_cos its column-normalised copy) and the
+// per-object uploads of harmony.py:240-271
+int hmx_upload(hmx_engine* e, const float* Z, const int32_t* static_cells, int64_t n_static_pos,
+               const int32_t* static_tile_group, int32_t n_static_tiles, const int32_t* group_cols, const float* Pr_b,
+               const float* theta, const float* sigma, const float* lamb, const int32_t* global_id,
+               const int32_t* source_row) {
+    ZSource z;
+    z.host = Z;
+    return upload_impl(e, z, static_cells, n_static_pos, static_tile_group, n_static_tiles, group_cols, Pr_b, theta, sigma,
+                       lamb, global_id, source_row);
+}
+
+// harmony.py:234-238 for a Z that already lives on the device (torch.tensor(Z, dtype=float32, device=device) of a
+// device tensor): read in place, converted to fp32 on the device; no host copy of the N x d embedding
+int hmx_upload_device(hmx_engine* e, const void* Z, int dtype, int64_t stride_cell, int64_t stride_pc, void* stream,
+                      const int32_t* static_cells, int64_t n_static_pos, const int32_t* static_tile_group, int32_t n_static_tiles,
+                      const int32_t* group_cols, const float* Pr_b, const float* theta, const float* sigma, const float* lamb,
+                      const int32_t* global_id, const int32_t* source_row) {
+    if (!Z) return fail(HMX_ERR_ARG, "null argument");
+    if (dtype != HMX_DTYPE_F32 && dtype != HMX_DTYPE_F16 && dtype != HMX_DTYPE_BF16 && dtype != HMX_DTYPE_F64)
+        return fail(HMX_ERR_ARG, "hmx_upload_device: unknown dtype %d", dtype);
+    if (stride_cell < 0 || stride_pc < 0) return fail(HMX_ERR_ARG, "hmx_upload_device: negative stride");
+    ZSource z;
+    z.dev = Z;
+    z.dtype = dtype;
+    z.s_cell = stride_cell;
+    z.s_pc = stride_pc;
+    z.caller = static_cast<hipStream_t>(stream);
+    return upload_impl(e, z, static_cells, n_static_pos, static_tile_group, n_static_tiles, group_cols, Pr_b, theta, sigma,
+                       lamb, global_id, source_row);
 }
 
 int hmx_compute_lisi(int32_t device_id, const double* X, int64_t n, int32_t d, const int32_t* label_codes, int32_t n_labels,
@@ -1974,6 +2066,29 @@ int hmx_get_rows(hmx_engine* e, int which, const int32_t* rows, int32_t n_rows, 
     d_rows.release();
     d_out.release();
     if (he != hipSuccess) return fail(HMX_ERR_HIP, "hmx_get_rows: %s", hipGetErrorString(he));
+    return HMX_OK;
+}
+
+// harmony.py:288-303 (Z_corr / Z_orig / Z_cos / R as cells x columns) without the trip through host memory
+int hmx_copy_out_device(hmx_engine* e, int which, void* dst, int64_t stride_cell, int64_t stride_col, void* stream) {
+    if (!e || !dst) return fail(HMX_ERR_ARG, "null argument");
+    if (which != HMX_Z_ORIG && which != HMX_Z_COS && which != HMX_Z_CORR && which != HMX_R)
+        return fail(HMX_ERR_ARG, "hmx_copy_out_device: not an N-sized float array (%d)", which);
+    if (stride_cell < 1 || stride_col < 1) return fail(HMX_ERR_ARG, "hmx_copy_out_device: strides must be >= 1");
+    if (!e->uploaded) return fail(HMX_ERR_STATE, "hmx_upload must come first");
+    if (!e->map_perm) return fail(HMX_ERR_STATE, "hmx_copy_out_device: the upload's source_row is not a permutation of the cells");
+    void* p; size_t need; int rows, cols, ld, elem, rc;
+    if ((rc = locate(e, which, &p, &need, &rows, &cols, &ld, &elem))) return rc;
+    if ((rc = use_device(e)) || (rc = io_events(e))) return rc;
+    hipStream_t caller = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipEventRecord(e->io_ev[0], caller));               // dst may still be in use on the caller's stream
+    HIP_TRY(hipStreamWaitEvent(e->stream, e->io_ev[0], 0));
+    if (io_uses_slab(stride_cell, stride_col) && (rc = ensure_inverse(e))) return rc;
+    launch_io_store(static_cast<const float*>(p), ld, cols, e->cell_map.p, cell_inverse(e), static_cast<float*>(dst), stride_cell,
+                    stride_col, e->N, e->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(e->io_ev[1], e->stream));            // the caller's later work sees the copy
+    HIP_TRY(hipStreamWaitEvent(caller, e->io_ev[1], 0));
     return HMX_OK;
 }
 

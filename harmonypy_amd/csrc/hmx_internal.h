@@ -288,6 +288,17 @@ struct SeedArgs {
 #define HMX_SEED_SLOTS 8
 void launch_kmeans_seed(const SeedArgs& a, int K, hipStream_t s);
 void launch_load_rows(const float* src, int d, const int* source_row, float* dst, int dp, int64_t N, hipStream_t s);
+// device I/O path (hmx_io.hip): the caller's tensor in its dtype and strides <-> the engine's padded, group-sorted rows.
+// map: internal row -> caller row, inv: caller row -> internal row (both null: identity).  launch_io_load returns
+// nonzero for an unknown dtype.  Cell stride 1 with another feature stride takes the LDS slab kernels, which need inv.
+struct IoSlab { int pitch, lg_s; };        // LDS tile of the slab kernels: 2^lg_s caller cells x pitch floats
+IoSlab io_slab(int cols);
+bool io_uses_slab(int64_t s_cell, int64_t s_feat);
+void launch_io_invert(const int* map, int* inv, int64_t N, hipStream_t s);
+int launch_io_load(const void* src, int dtype, int64_t s_cell, int64_t s_pc, const int* map, const int* inv, float* dst, int d,
+                   int dp, int64_t N, hipStream_t s);
+void launch_io_store(const float* src, int ld, int cols, const int* map, const int* inv, float* dst, int64_t s_cell, int64_t s_col,
+                     int64_t N, hipStream_t s);
 size_t kmeans_slab_floats(int wgs, int K16, int dp);
 int launch_kmeans_step(const float* Zcos, const float* C, const float* hn, const int* cells, int n_tiles, float* slab, int K,
                        int K16, int dp, int ldy, int wgs, hipStream_t s);

@@ -101,6 +101,46 @@ def _device_index(device):
     return int(idx) if idx else 0
 
 
+_DLPACK_ROCM = 10   # DLDeviceType kDLROCM
+
+
+def _as_device_tensor(x):
+    """The torch view of an embedding that lives on a HIP device -- a ``torch.Tensor`` there, or any ``__dlpack__``
+    producer whose device is ROCm (``torch.from_dlpack``, no copy) -- or None for host data (NumPy, CPU tensors)."""
+    import torch
+    if isinstance(x, torch.Tensor):
+        return x if x.device.type == "cuda" else None
+    if hasattr(x, "__dlpack__") and hasattr(x, "__dlpack_device__"):
+        if int(x.__dlpack_device__()[0]) == _DLPACK_ROCM:
+            return torch.from_dlpack(x)
+    return None
+
+
+def _device_dtype(t):
+    """HMX_DTYPE_* of a device tensor; ValueError for anything but float32 / float16 / bfloat16 / float64 matrices."""
+    import torch
+    codes = {torch.float32: _capi.HMX_DTYPE_F32, torch.float16: _capi.HMX_DTYPE_F16,
+             torch.bfloat16: _capi.HMX_DTYPE_BF16, torch.float64: _capi.HMX_DTYPE_F64}
+    if t.dim() != 2:
+        raise ValueError(f"data_mat on the device must be a matrix, got {t.dim()} dimension(s)")
+    if t.dtype not in codes:
+        raise ValueError(f"data_mat on the device must be float32, float16, bfloat16 or float64, got {t.dtype}")
+    return codes[t.dtype]
+
+
+def _engine_device(device, t=None):
+    """Device ordinal of the engine: ``device`` (see _device_index), or with a device tensor its own device -- a
+    ``device`` that names another ordinal is a ValueError."""
+    if t is None:
+        return _device_index(device)
+    own = t.device.index if t.device.index is not None else 0
+    if device is not None:
+        named = _device_index(device)
+        if ":" in str(device) and named != own:
+            raise ValueError(f"device={device!r} but data_mat lives on cuda:{own}")
+    return own
+
+
 def run_harmony(
     data_mat: np.ndarray,
     meta_data: pd.DataFrame,
@@ -136,6 +176,11 @@ def run_harmony(
     slice) and gets back an object over those cells; batch proportions, cluster count, blocks,
     centroids and corrections are those of the whole job (``dist.py``).
 
+    ``data_mat`` may also live on the GPU: a 2-D ``torch.Tensor`` on a HIP device, or any ``__dlpack__``
+    producer on ROCm, of float32 / float16 / bfloat16 / float64 and any strides (``pcs[:, :50]``, ``.T``
+    views).  It is then read in place on its device (``device=None`` follows it) and never copied to the
+    host; ``Harmony.to_tensor`` hands the results back as device tensors.
+
     ``_y0`` / ``_schedule`` (keyword only, not in the reference): replay aids of the parity tests
     and of ``bench.py`` -- ``_y0`` is a d x K matrix of initial centroids used instead of the
     k-means initialisation (harmony.py:369-373), ``_schedule`` a list of k-means round counts,
@@ -144,7 +189,7 @@ def run_harmony(
     """
     _validate_arguments(nclust, block_size, meta_data, vars_use)
     p = _prepare_inputs(data_mat, meta_data, vars_use, theta, lamb, sigma, nclust, tau, shard=shard)
-    dev = _device_index(device)
+    dev = _engine_device(device, p["Z"] if p["on_device"] else None)
     if verbose:
         logger.info(f"Running Harmony (HIP engine on MI355X device {dev})")
         logger.info("  Parameters:")
@@ -193,13 +238,23 @@ def _prepare_inputs(data_mat, meta_data, vars_use, theta=None, lamb=None, sigma=
     design kept as integer codes instead of a dense one-hot matrix.  With ``shard`` the inputs
     are this rank's slice; cell counts, batch levels and batch sizes are those of the whole job."""
     N = meta_data.shape[0]
-    if hasattr(data_mat, "values"):
-        data_mat = data_mat.values
-    data_mat = np.asarray(data_mat)
-    if data_mat.shape[1] != N:                                  # harmony.py:117-118
-        data_mat = data_mat.T
-    assert data_mat.shape[1] == N, \
-        "data_mat and meta_data do not have the same number of cells"
+    on_device = _as_device_tensor(data_mat)
+    if on_device is not None:
+        # the embedding stays where it is: a d x N view of the caller's tensor, whatever its strides and dtype
+        _device_dtype(on_device)
+        data_mat = on_device
+        if data_mat.shape[1] != N:                              # harmony.py:117-118 (a view, not a copy)
+            data_mat = data_mat.T
+        if data_mat.shape[1] != N:
+            raise ValueError(f"data_mat {tuple(on_device.shape)} and meta_data ({N} cells) do not have the same number of cells")
+    else:
+        if hasattr(data_mat, "values") and not callable(data_mat.values):   # (a CPU tensor's .values is a method)
+            data_mat = data_mat.values
+        data_mat = np.asarray(data_mat)
+        if data_mat.shape[1] != N:                              # harmony.py:117-118
+            data_mat = data_mat.T
+        assert data_mat.shape[1] == N, \
+            "data_mat and meta_data do not have the same number of cells"
     if data_mat.shape[0] > _capi.HMX_MAX_PCS:
         raise ValueError(f"{data_mat.shape[0]} PCs: this build supports up to {_capi.HMX_MAX_PCS}")
 
@@ -277,7 +332,8 @@ def _prepare_inputs(data_mat, meta_data, vars_use, theta=None, lamb=None, sigma=
     if tau > 0:                                                        # harmony.py:172-173
         theta = theta * (1 - np.exp(-(N_b / (nclust * tau)) ** 2))
 
-    return dict(Z=np.asarray(data_mat, dtype=np.float32), codes=BatchCodes(codes, B), Pr_b=Pr_b,
+    return dict(Z=data_mat if on_device is not None else np.asarray(data_mat, dtype=np.float32), on_device=on_device is not None,
+                codes=BatchCodes(codes, B), Pr_b=Pr_b,
                 sigma=sigma.astype(np.float32), theta=np.asarray(theta, dtype=np.float32), lamb=lamb,
                 lambda_estimation=lambda_estimation, K=int(nclust), vars_use=list(vars_use))
 
@@ -377,9 +433,11 @@ def build_block_lists(update_order, rank, gid_int, n_blocks, cells_per_block, G,
 class Harmony:
     """Device-resident Harmony state with the reference's object API (harmony.py:218-569).
 
-    ``Z`` is d x N (PCs x cells) like the reference's; ``Phi`` is the dense B x N indicator
+    ``Z`` is d x N (PCs x cells) like the reference's -- a host array, or a tensor on a HIP device
+    (see ``run_harmony``), which is read where it lies; ``Phi`` is the dense B x N indicator
     matrix of the reference or a ``BatchCodes``.  The constructor runs the whole algorithm
-    (harmony.py:280-282); results are read through the same properties.
+    (harmony.py:280-282); results are read through the same properties, or as device tensors
+    through ``to_tensor``.
     """
 
     def __init__(
@@ -390,7 +448,13 @@ class Harmony:
     ):
         self.device = device
         self.shard = shard
-        Z = np.asarray(Z, dtype=np.float32)
+        Zdev = _as_device_tensor(Z)
+        if Zdev is not None:
+            _device_dtype(Zdev)
+            Z = Zdev
+        else:
+            Z = np.asarray(Z, dtype=np.float32)
+        self._device_id = _engine_device(device, Zdev)
         self.d, self.N = Z.shape
         # cells of the whole job and this rank's first global cell id (N_global == N unsharded)
         self._offset, self.N_global = (0, self.N) if shard is None else shard.layout(self.N)
@@ -479,10 +543,22 @@ class Harmony:
 
         self._engine = _capi.Engine(self.N, self.d, self.K, self.B, self._G, V, self._n_blocks,
                                     lambda_estimation=self.lambda_estimation, alpha=self.alpha,
-                                    device_id=_device_index(self.device), n_cells_global=self.N_global)
+                                    device_id=self._device_id, n_cells_global=self.N_global)
         self.transport = None if self.shard is None else self.shard.attach(self._engine)
         self._lap("engine_create")
-        if Z is not None:
+        if Z is not None and not isinstance(Z, np.ndarray):
+            # a device tensor (d x N view): the engine reads it in place, in its dtype and strides, ordered behind the
+            # work queued on the caller's current stream; same regrouping and ids as below
+            import torch
+            src = self._order.astype(np.int32)
+            gid = src if self._offset == 0 else (self._offset + self._order).astype(np.int32)
+            self._engine.upload_device(Z.data_ptr(), _device_dtype(Z), Z.stride(1), Z.stride(0),
+                                       torch.cuda.current_stream(Z.device).cuda_stream,
+                                       self._static_cells, self._static_tile_grp, self._group_cols, self._Pr_b,
+                                       self._theta, self._sigma, None if self.lambda_estimation else self._lamb,
+                                       global_id=gid, source_row=src)
+            self._lap("upload_device")
+        elif Z is not None:
             # Z travels cells x d in the caller's order; the device regroups it (source_row).
             # A cell's id in the whole job = its row in the unsharded input.
             src = self._order.astype(np.int32)
@@ -500,6 +576,34 @@ class Harmony:
         res = np.empty_like(out)
         res[self._order] = out                    # internal (group-sorted) rows back to the caller's order
         return res
+
+    _DEVICE_ARRAYS = {"Z_corr": _capi.HMX_Z_CORR, "Z_orig": _capi.HMX_Z_ORIG, "Z_cos": _capi.HMX_Z_COS, "R": _capi.HMX_R}
+
+    def to_tensor(self, which="Z_corr", out=None):
+        """``Z_corr`` / ``Z_orig`` / ``Z_cos`` / ``R`` as a float32 torch tensor on the engine's device: cells x
+        features in the caller's cell order, the same values as the NumPy property, without a trip through the host.
+
+        ``out``: a float32 tensor of that shape on that device, any strides (a d x N view, a column slice of a wider
+        matrix); written in place, nothing outside the view is touched.  The copy is ordered on the current stream."""
+        import torch
+        if which not in self._DEVICE_ARRAYS:
+            raise ValueError(f"which={which!r}: expected one of {sorted(self._DEVICE_ARRAYS)}")
+        shape = (self.N, self.K if which == "R" else self.d)
+        dev = torch.device("cuda", self._device_id)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=dev)
+        else:
+            if not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.float32:
+                raise ValueError(f"out must be a float32 tensor on {dev}")
+            if tuple(out.shape) != shape:
+                raise ValueError(f"out has shape {tuple(out.shape)}, {which} is {shape}")
+            if any(st < 1 and n > 1 for st, n in zip(out.stride(), out.shape)):
+                raise ValueError("out must not overlap itself (a stride of 0)")
+        # a dimension of one element may carry any stride: give the library a valid one
+        sc, sf = (st if n > 1 else 1 for st, n in zip(out.stride(), out.shape))
+        self._engine.copy_out_device(self._DEVICE_ARRAYS[which], out.data_ptr(), sc, sf,
+                                     torch.cuda.current_stream(dev).cuda_stream)
+        return out
 
     @property
     def _rank(self):
