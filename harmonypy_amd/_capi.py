@@ -30,7 +30,7 @@ EXPORTS = [
     "hmx_build_id", "hmx_cluster", "hmx_set_timing_stride", "hmx_set_timing_families", "hmx_kmeans_lloyd", "hmx_can_lloyd", "hmx_kmeans_seed", "hmx_compute_lisi", "hmx_get_rows", "hmx_set_ranks", "hmx_peer_export", "hmx_peer_attach", "hmx_peer_selftest", "hmx_peer_enable",
 ]
 # include/hmx_device_io.h: the device I/O path (same ABI version; its own header, see there)
-DEVICE_IO_EXPORTS = ["hmx_upload_device", "hmx_copy_out_device"]
+DEVICE_IO_EXPORTS = ["hmx_upload_device", "hmx_copy_out_device", "hmx_compute_lisi_device"]
 HMX_PEER_HANDLE_BYTES = 64
 HMX_ABI_VERSION = 8
 HMX_UNIQUE_ID_BYTES = 128
@@ -81,6 +81,7 @@ def load():
     lib.hmx_copy_out_device.argtypes = [vp, C.c_int, vp, i64, i64, vp]
     lib.hmx_kmeans_seed.argtypes = [vp, vp, i64, C.c_uint64, vp, vp]
     lib.hmx_compute_lisi.argtypes = [i32, vp, i64, i32, vp, i32, C.c_double, vp, vp, vp]
+    lib.hmx_compute_lisi_device.argtypes = [i32, vp, C.c_int, i64, i32, i64, i64, vp, vp, i32, C.c_double, vp, vp, vp]
     lib.hmx_comm_unique_id.argtypes = [vp]
     lib.hmx_comm_init.argtypes = [vp, vp, C.c_int, C.c_int]
     lib.hmx_set_host_allreduce.argtypes = [vp, HOST_ALLREDUCE_FN, vp]

@@ -802,12 +802,26 @@ int hmx_upload_device(hmx_engine* e, const void* Z, int dtype, int64_t stride_ce
                        lamb, global_id, source_row);
 }
 
-int hmx_compute_lisi(int32_t device_id, const double* X, int64_t n, int32_t d, const int32_t* label_codes, int32_t n_labels,
-                     double perplexity, double* lisi_out, double* knn_dist_out, int32_t* knn_idx_out) {
-    if (!X || !label_codes || !lisi_out) return fail(HMX_ERR_ARG, "null argument");
+namespace {
+
+// Where the LISI input comes from: host memory (n x d float64, row-major) or a caller's device tensor (HMX_DTYPE_*,
+// element (r, c) at dev + r * s_cell + c * s_col), read on the caller's stream.
+struct LisiSource {
+    const double* host = nullptr;
+    const void* dev = nullptr;
+    int dtype = HMX_DTYPE_F64;
+    int64_t s_cell = 0, s_col = 0;
+    hipStream_t stream = nullptr;
+};
+
+// lisi.py:24-133 on the device, for both entry points.  Outputs: host arrays for a host source (copied back through
+// device buffers), device arrays for a device source (written by k_lisi_finish in place).
+int lisi_impl(int32_t device_id, const LisiSource& src, int64_t n, int32_t d, const int32_t* label_codes, int32_t n_labels,
+              double perplexity, double* lisi_out, double* knn_dist_out, int32_t* knn_idx_out) {
+    if (!(src.host || src.dev) || !label_codes || !lisi_out) return fail(HMX_ERR_ARG, "null argument");
     if ((knn_dist_out == nullptr) != (knn_idx_out == nullptr)) return fail(HMX_ERR_ARG, "knn_dist_out and knn_idx_out go together");
     if (n < 1 || n > (int64_t)1 << 31) return fail(HMX_ERR_ARG, "n out of range");
-    if (d < 1 || d > 208) return fail(HMX_ERR_ARG, "d must be in [1, 208]");
+    if (d < 1 || d > HMX_MAX_PCS) return fail(HMX_ERR_ARG, "d must be in [1, %d]", HMX_MAX_PCS);
     if (n_labels < 1) return fail(HMX_ERR_ARG, "n_labels must be >= 1");
     const int nn = (int)(perplexity * 3);                                     // lisi.py:53
     // the float32 pass keeps the best cap / 2 candidates of a query for the exact float64 ranking: 8 of them are slack for
@@ -820,6 +834,7 @@ int hmx_compute_lisi(int32_t device_id, const double* X, int64_t n, int32_t d, c
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (device_id < 0 || device_id >= ndev) return fail(HMX_ERR_ARG, "device %d not present (%d devices)", device_id, ndev);
     HIP_TRY(hipSetDevice(device_id));
+    const bool on_dev = src.dev != nullptr;
     const int dp = (d + 15) & ~15;
     const int64_t npad = (n + 255) & ~(int64_t)255;
     const int M = nn - 1;
@@ -832,15 +847,22 @@ int hmx_compute_lisi(int32_t device_id, const double* X, int64_t n, int32_t d, c
         ~Release() { a.release(); b.release(); c.release(); d2.release(); f.release(); g.release(); h.release(); i.release(); j.release(); k.release(); }
     } guard{X64, sums, out, kd, X32, cn, lists, counts, labels, ki};
     int rc;
-    if ((rc = X64.reserve((size_t)n * d)) || (rc = sums.reserve(d)) || (rc = out.reserve((size_t)n * n_labels)) ||
-        (rc = X32.reserve((size_t)npad * dp)) || (rc = cn.reserve(npad)) || (rc = lists.reserve((size_t)npad * cap)) ||
-        (rc = counts.reserve(n)) || (rc = labels.reserve((size_t)n * n_labels)))
+    if ((rc = X64.reserve((size_t)n * d)) || (rc = sums.reserve(d)) || (rc = X32.reserve((size_t)npad * dp)) || (rc = cn.reserve(npad)) ||
+        (rc = lists.reserve((size_t)npad * cap)) || (rc = counts.reserve(n)) || (rc = labels.reserve((size_t)n * n_labels)))
         return rc;
-    if (knn_dist_out && ((rc = kd.reserve((size_t)n * M)) || (rc = ki.reserve((size_t)n * M)))) return rc;
-    hipStream_t s = nullptr;                                                  // the device's default stream
-    HIP_TRY(hipMemcpyAsync(X64.p, X, (size_t)n * d * sizeof(double), hipMemcpyHostToDevice, s));
+    if (!on_dev && ((rc = out.reserve((size_t)n * n_labels)) || (knn_dist_out && ((rc = kd.reserve((size_t)n * M)) || (rc = ki.reserve((size_t)n * M))))))
+        return rc;
+    // host input: the device's default stream; device input: the caller's stream, so that the call is ordered behind
+    // whatever produced X there and whatever comes next there sees the results
+    hipStream_t s = src.stream;
     HIP_TRY(hipMemcpyAsync(labels.p, label_codes, (size_t)n * n_labels * sizeof(int), hipMemcpyHostToDevice, s));
-    launch_lisi_prepare(X64.p, n, npad, d, dp, sums.p, X32.p, cn.p, s);
+    if (on_dev) {
+        if (launch_lisi_prepare_device(src.dev, src.dtype, src.s_cell, src.s_col, n, npad, d, dp, X64.p, sums.p, X32.p, cn.p, s))
+            return fail(HMX_ERR_ARG, "unknown dtype %d", src.dtype);
+    } else {
+        HIP_TRY(hipMemcpyAsync(X64.p, src.host, (size_t)n * d * sizeof(double), hipMemcpyHostToDevice, s));
+        launch_lisi_prepare(X64.p, n, npad, d, dp, sums.p, X32.p, cn.p, s);
+    }
     LisiKnnArgs ka{};
     ka.X = X32.p; ka.cn = cn.p; ka.n = n; ka.npad = npad; ka.dp = dp; ka.lists = lists.p; ka.counts = counts.p; ka.cap = cap;
 #ifdef LISI_PROF
@@ -853,7 +875,8 @@ int hmx_compute_lisi(int32_t device_id, const double* X, int64_t n, int32_t d, c
 #ifdef LISI_PROF
     {
         unsigned long long h[8];
-        HIP_TRY(hipMemcpy(h, prof.p, sizeof h, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpyAsync(h, prof.p, sizeof h, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
         const double waves = (double)npad / 64.0, tiles = (double)((n + 15) / 16);
         fprintf(stderr, "[lisi prof] cycles per tile per wave: loads-issue %.0f, fragments+MFMA %.0f, store pieces (load wait) %.0f, append %.0f, barrier %.0f\n",
                 h[0] / waves / tiles, h[1] / waves / tiles, h[2] / waves / tiles, h[3] / waves / tiles, h[4] / waves / tiles);
@@ -863,16 +886,49 @@ int hmx_compute_lisi(int32_t device_id, const double* X, int64_t n, int32_t d, c
     LisiFinishArgs fa{};
     fa.X = X64.p; fa.n = n; fa.d = d; fa.nn = nn; fa.n_labels = n_labels; fa.lists = lists.p; fa.counts = counts.p; fa.cap = cap;
     fa.labels = labels.p; fa.perplexity = perplexity; fa.tol = 1e-5;         // lisi.py:75
-    fa.out = out.p; fa.knn_dist = kd.p; fa.knn_idx = ki.p;
-    launch_lisi_finish(fa, s);
-    HIP_TRY(hipMemcpyAsync(lisi_out, out.p, (size_t)n * n_labels * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (knn_dist_out) {
-        HIP_TRY(hipMemcpyAsync(knn_dist_out, kd.p, (size_t)n * M * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(knn_idx_out, ki.p, (size_t)n * M * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (on_dev) {
+        fa.out = lisi_out; fa.knn_dist = knn_dist_out; fa.knn_idx = knn_idx_out;
+    } else {
+        fa.out = out.p; fa.knn_dist = kd.p; fa.knn_idx = ki.p;
     }
-    HIP_TRY(hipStreamSynchronize(s));
+    launch_lisi_finish(fa, s);
+    if (!on_dev) {
+        HIP_TRY(hipMemcpyAsync(lisi_out, out.p, (size_t)n * n_labels * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (knn_dist_out) {
+            HIP_TRY(hipMemcpyAsync(knn_dist_out, kd.p, (size_t)n * M * sizeof(double), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(knn_idx_out, ki.p, (size_t)n * M * sizeof(int), hipMemcpyDeviceToHost, s));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(s));                                         // (the temporaries are released on return)
     HIP_TRY(hipGetLastError());
     return HMX_OK;
+}
+
+}  // namespace
+
+int hmx_compute_lisi(int32_t device_id, const double* X, int64_t n, int32_t d, const int32_t* label_codes, int32_t n_labels,
+                     double perplexity, double* lisi_out, double* knn_dist_out, int32_t* knn_idx_out) {
+    LisiSource src;
+    src.host = X;
+    return lisi_impl(device_id, src, n, d, label_codes, n_labels, perplexity, lisi_out, knn_dist_out, knn_idx_out);
+}
+
+// compute_lisi of a cells x features tensor that lives on the device: read in place, converted exactly to float64 on the
+// device; no host copy of X, the results written into the caller's device arrays
+int hmx_compute_lisi_device(int32_t device_id, const void* X, int dtype, int64_t n, int32_t d, int64_t stride_cell,
+                            int64_t stride_col, void* stream, const int32_t* label_codes, int32_t n_labels, double perplexity,
+                            double* lisi_out, double* knn_dist_out, int32_t* knn_idx_out) {
+    if (!X) return fail(HMX_ERR_ARG, "null argument");
+    if (dtype != HMX_DTYPE_F32 && dtype != HMX_DTYPE_F16 && dtype != HMX_DTYPE_BF16 && dtype != HMX_DTYPE_F64)
+        return fail(HMX_ERR_ARG, "hmx_compute_lisi_device: unknown dtype %d", dtype);
+    if (stride_cell < 0 || stride_col < 0) return fail(HMX_ERR_ARG, "hmx_compute_lisi_device: negative stride");
+    LisiSource src;
+    src.dev = X;
+    src.dtype = dtype;
+    src.s_cell = stride_cell;
+    src.s_col = stride_col;
+    src.stream = static_cast<hipStream_t>(stream);
+    return lisi_impl(device_id, src, n, d, label_codes, n_labels, perplexity, lisi_out, knn_dist_out, knn_idx_out);
 }
 
 int hmx_kmeans_seed(hmx_engine* e, const float* points, int64_t n_points, uint64_t seed, float* centers_out, int32_t* chosen_out) {

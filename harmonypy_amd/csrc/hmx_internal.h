@@ -267,6 +267,10 @@ struct LisiFinishArgs {
     int* knn_idx;
 };
 void launch_lisi_prepare(const double* X, int64_t n, int64_t npad, int d, int dp, double* sums, float* X32, float* cn, hipStream_t s);
+// the same from a caller's device tensor (HMX_DTYPE_*, element (r, c) at src + r * s_cell + c * s_col): also fills X
+// (n x d float64); 1 for an unknown dtype
+int launch_lisi_prepare_device(const void* src, int dtype, int64_t s_cell, int64_t s_col, int64_t n, int64_t npad, int d, int dp,
+                               double* X, double* sums, float* X32, float* cn, hipStream_t s);
 int launch_lisi_knn(const LisiKnnArgs& a, hipStream_t s);
 int lisi_list_cap(int nn);          // 0: more neighbours than the largest list ranks
 void launch_lisi_finish(const LisiFinishArgs& a, hipStream_t s);

@@ -4,6 +4,9 @@
 //
 //   k_lisi_colsum / k_lisi_center : centre the float64 input, float32 copy padded to 16-float rows,
 //                                   squared norms (padding rows get +inf and never qualify)
+//   k_lisi_load<T>                : a caller's device tensor (float32 / float16 / bfloat16 / float64, any
+//                                   strides) read in place into the float64 n x d matrix, converted exactly,
+//                                   with k_lisi_colsum's column sums on the way (hmx_compute_lisi_device)
 //   k_lisi_knn<KS16, QT>          : brute-force neighbour search.  A wave owns 16*QT queries whose
 //                                   fragments stay in registers and streams every 16-candidate tile
 //                                   (shared by the workgroup's waves through LDS) through f32 MFMA, turns them into
@@ -21,6 +24,7 @@
 
 #include <cstdint>
 
+#include "hmx_device_io.h"
 #include "hmx_internal.h"
 
 namespace {
@@ -49,13 +53,42 @@ __device__ __forceinline__ float order_float(unsigned k) {
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
 }
 
+// one thread per column (d may exceed the workgroup: up to HMX_MAX_PCS), 1024 rows per workgroup
 __global__ __launch_bounds__(256) void k_lisi_colsum(const double* __restrict__ X, int64_t n, int d, double* __restrict__ sums) {
-    const int c = threadIdx.x;
-    if (c >= d) return;
     const int64_t r0 = (int64_t)blockIdx.x * 1024, r1 = min(n, r0 + 1024);
-    double s = 0.0;
-    for (int64_t r = r0; r < r1; ++r) s += X[r * d + c];
-    atomicAdd(sums + c, s);
+    for (int c = threadIdx.x; c < d; c += 256) {
+        double s = 0.0;
+        for (int64_t r = r0; r < r1; ++r) s += X[r * d + c];
+        atomicAdd(sums + c, s);
+    }
+}
+
+struct bf16_t { uint16_t u; };
+__device__ __forceinline__ double to_f64(double v) { return v; }
+__device__ __forceinline__ double to_f64(float v) { return (double)v; }                                // every conversion exact
+__device__ __forceinline__ double to_f64(_Float16 v) { return (double)(float)v; }
+__device__ __forceinline__ double to_f64(bf16_t v) { return (double)__uint_as_float((unsigned)v.u << 16); }
+
+// k_lisi_colsum's layout with the source read in place: element (row r, column c) at src + r * s_cell + c * s_col.
+// A row-major source is read along the rows by the lanes of a wave; a d x n one (cell stride 1) along the cells by
+// every lane, whose column stays in the cache for the next rows.  The float64 rows are written contiguously.
+// LISI_LOAD_ROWS rows per workgroup; the row loop is unrolled so that several loads of a lane are in flight.
+#define LISI_LOAD_ROWS 256
+template <typename T>
+__global__ __launch_bounds__(256) void k_lisi_load(const T* __restrict__ src, int64_t s_cell, int64_t s_col, int64_t n, int d,
+                                                   double* __restrict__ X, double* __restrict__ sums) {
+    const int64_t r0 = (int64_t)blockIdx.x * LISI_LOAD_ROWS, r1 = min(n, r0 + LISI_LOAD_ROWS);
+    for (int c = threadIdx.x; c < d; c += 256) {
+        const T* col = src + (int64_t)c * s_col;
+        double s = 0.0;
+#pragma unroll 8
+        for (int64_t r = r0; r < r1; ++r) {
+            const double v = to_f64(col[r * s_cell]);
+            X[r * d + c] = v;
+            s += v;
+        }
+        atomicAdd(sums + c, s);
+    }
 }
 
 // 16 lanes per row; rows >= n are padding
@@ -97,14 +130,35 @@ __device__ __forceinline__ void wave_sort(unsigned long long* scr, int lane) {
 // Candidate lists come in three sizes (CAP entries, the best CAP / 2 kept by a compaction and ranked exactly afterwards):
 // 256 for 3 * perplexity <= 120 neighbours (the reference's default is 90), 1024 up to 504, 4096 up to 2040.  The large
 // sizes keep the sort scratch in dynamic LDS (32 KB / 128 KB per workgroup) and so run fewer workgroups per CU.
+//
+// Above 208 features (KS16 14..20, QT 1) two things change, both by constexpr so that the instances up to 208 are
+// compiled as before:
+//  - registers: the query fragments alone are 4 * KS16 VGPRs (80 at 320 features), the tile fragments as many again,
+//    plus the prefetch pieces (8 * NPC) -- 192 at KS16 = 20, more than the 168 of three waves per SIMD.  The 256-entry
+//    lists there ask for two (256 registers; KS16 14..16 still fit in 168), the larger lists keep asking for one;
+//  - LDS: the sort scratch of the 4096-entry lists (4 waves x 32 KB) plus two staging buffers of 16 x (16 * KS16 + 4)
+//    floats exceed the CU's 160 KB from KS16 = 16 on.  Those instances stage through ONE buffer and take a second
+//    barrier per tile, between the fragment reads of tile t and the store of tile t+1 (every wave has multiplied by
+//    then).  Fewer waves per workgroup would keep the single barrier but multiply the workgroup's global / L2 reads
+//    of every candidate tile; halving the feature dimension would split the query fragments across two passes.  The
+//    4096-entry lists (3 * perplexity > 504) are dominated by their compaction sorts anyway.
 template <int KS16, int QT, int CAP>
-__global__ __launch_bounds__(64 * LISI_KNN_WAVES, CAP == 256 ? 3 : 1) void k_lisi_knn(LisiKnnArgs a) {
+constexpr int knn_stage_buffers() {
+    constexpr size_t fixed = (size_t)LISI_KNN_WAVES * CAP * 8 + (size_t)LISI_KNN_WAVES * 16 * QT * 4 * 2;   // scratch, cnt, tau
+    return fixed + 2 * 16 * (16 * KS16 + 4) * 4 <= 160 * 1024 ? 2 : 1;
+}
+
+template <int KS16, int QT, int CAP>
+__global__ __launch_bounds__(64 * LISI_KNN_WAVES, CAP == 256 ? (KS16 <= 13 ? 3 : 2) : 1) void k_lisi_knn(LisiKnnArgs a) {
     constexpr int KEEP = CAP / 2;
+    constexpr int NSTAGE = knn_stage_buffers<KS16, QT, CAP>();
     extern __shared__ __attribute__((aligned(16))) unsigned long long scr_all[];   // waves x CAP
     __shared__ int cnt_all[LISI_KNN_WAVES][16 * QT];
     __shared__ float tau_all[LISI_KNN_WAVES][16 * QT];
     constexpr int LDW = 16 * KS16 + 4;                       // padded row: conflict-free 16-byte fragment reads
-    __shared__ __attribute__((aligned(16))) float stage[2][16 * LDW];
+    __shared__ __attribute__((aligned(16))) float stage[NSTAGE][16 * LDW];
+    static_assert((size_t)LISI_KNN_WAVES * CAP * 8 + sizeof(cnt_all) + sizeof(tau_all) + sizeof(stage) <= 160 * 1024,
+                  "k_lisi_knn: LDS over the CU's 160 KB");
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int c16 = lane & 15, q = lane >> 4;
     unsigned long long* scr = scr_all + (size_t)wv * CAP;
@@ -166,6 +220,7 @@ __global__ __launch_bounds__(64 * LISI_KNN_WAVES, CAP == 256 ? 3 : 1) void k_lis
         }
     };
     auto store_pieces = [&](int ps, int sb) {
+        if constexpr (NSTAGE == 1) sb = 0;
 #pragma unroll
         for (int j = 0; j < NPC; ++j) {
             const int i = tid + 64 * LISI_KNN_WAVES * j;
@@ -174,6 +229,7 @@ __global__ __launch_bounds__(64 * LISI_KNN_WAVES, CAP == 256 ? 3 : 1) void k_lis
         }
     };
     auto read_fragments = [&](int sb) {
+        if constexpr (NSTAGE == 1) sb = 0;
 #pragma unroll
         for (int m = 0; m < KS16; ++m) af[m] = *reinterpret_cast<const f32x4*>(&stage[sb][c16 * LDW + 16 * m + 4 * q]);
     };
@@ -269,6 +325,7 @@ __global__ __launch_bounds__(64 * LISI_KNN_WAVES, CAP == 256 ? 3 : 1) void k_lis
                 multiply(p);
                 __builtin_amdgcn_sched_barrier(0);
                 LISI_STAMP(1)
+                if constexpr (NSTAGE == 1) __syncthreads();             // one buffer: every wave has read tile t
                 if (more) store_pieces(p ^ 1, p ^ 1);
                 __builtin_amdgcn_sched_barrier(0);
                 LISI_STAMP(2)
@@ -454,6 +511,28 @@ void launch_lisi_prepare(const double* X, int64_t n, int64_t npad, int d, int dp
     hipLaunchKernelGGL(k_lisi_center, dim3((unsigned)(npad / 16)), dim3(256), 0, s, X, n, npad, d, dp, sums, X32, cn);
 }
 
+namespace {
+template <typename T>
+void load_as(const void* src, int64_t s_cell, int64_t s_col, int64_t n, int d, double* X, double* sums, hipStream_t s) {
+    hipLaunchKernelGGL(k_lisi_load<T>, dim3((unsigned)((n + LISI_LOAD_ROWS - 1) / LISI_LOAD_ROWS)), dim3(256), 0, s,
+                       static_cast<const T*>(src), s_cell, s_col, n, d, X, sums);
+}
+}  // namespace
+
+int launch_lisi_prepare_device(const void* src, int dtype, int64_t s_cell, int64_t s_col, int64_t n, int64_t npad, int d, int dp,
+                               double* X, double* sums, float* X32, float* cn, hipStream_t s) {
+    (void)hipMemsetAsync(sums, 0, sizeof(double) * d, s);
+    switch (dtype) {
+        case HMX_DTYPE_F32: load_as<float>(src, s_cell, s_col, n, d, X, sums, s); break;
+        case HMX_DTYPE_F16: load_as<_Float16>(src, s_cell, s_col, n, d, X, sums, s); break;
+        case HMX_DTYPE_BF16: load_as<bf16_t>(src, s_cell, s_col, n, d, X, sums, s); break;
+        case HMX_DTYPE_F64: load_as<double>(src, s_cell, s_col, n, d, X, sums, s); break;
+        default: return 1;
+    }
+    hipLaunchKernelGGL(k_lisi_center, dim3((unsigned)(npad / 16)), dim3(256), 0, s, X, n, npad, d, dp, sums, X32, cn);
+    return 0;
+}
+
 int launch_lisi_knn(const LisiKnnArgs& a, hipStream_t s) {
     switch (a.dp / 16) {
         case 1: launch_knn_qt<1>(a, s); break;
@@ -469,6 +548,13 @@ int launch_lisi_knn(const LisiKnnArgs& a, hipStream_t s) {
         case 11: launch_knn_qt<11>(a, s); break;
         case 12: launch_knn_qt<12>(a, s); break;
         case 13: launch_knn_qt<13>(a, s); break;
+        case 14: launch_knn_qt<14>(a, s); break;
+        case 15: launch_knn_qt<15>(a, s); break;
+        case 16: launch_knn_qt<16>(a, s); break;
+        case 17: launch_knn_qt<17>(a, s); break;
+        case 18: launch_knn_qt<18>(a, s); break;
+        case 19: launch_knn_qt<19>(a, s); break;
+        case 20: launch_knn_qt<20>(a, s); break;
         default: return 1;
     }
     return 0;

@@ -116,19 +116,20 @@ def _as_device_tensor(x):
     return None
 
 
-def _device_dtype(t):
-    """HMX_DTYPE_* of a device tensor; ValueError for anything but float32 / float16 / bfloat16 / float64 matrices."""
+def _device_dtype(t, name="data_mat"):
+    """HMX_DTYPE_* of a device tensor; ValueError for anything but float32 / float16 / bfloat16 / float64 matrices.
+    ``name``: the argument the messages name."""
     import torch
     codes = {torch.float32: _capi.HMX_DTYPE_F32, torch.float16: _capi.HMX_DTYPE_F16,
              torch.bfloat16: _capi.HMX_DTYPE_BF16, torch.float64: _capi.HMX_DTYPE_F64}
     if t.dim() != 2:
-        raise ValueError(f"data_mat on the device must be a matrix, got {t.dim()} dimension(s)")
+        raise ValueError(f"{name} on the device must be a matrix, got {t.dim()} dimension(s)")
     if t.dtype not in codes:
-        raise ValueError(f"data_mat on the device must be float32, float16, bfloat16 or float64, got {t.dtype}")
+        raise ValueError(f"{name} on the device must be float32, float16, bfloat16 or float64, got {t.dtype}")
     return codes[t.dtype]
 
 
-def _engine_device(device, t=None):
+def _engine_device(device, t=None, name="data_mat"):
     """Device ordinal of the engine: ``device`` (see _device_index), or with a device tensor its own device -- a
     ``device`` that names another ordinal is a ValueError."""
     if t is None:
@@ -137,7 +138,7 @@ def _engine_device(device, t=None):
     if device is not None:
         named = _device_index(device)
         if ":" in str(device) and named != own:
-            raise ValueError(f"device={device!r} but data_mat lives on cuda:{own}")
+            raise ValueError(f"device={device!r} but {name} lives on cuda:{own}")
     return own
 
 

@@ -151,7 +151,8 @@ int hmx_peer_enable(hmx_engine* e, int on);
 int hmx_init_cluster(hmx_engine* e, const float* Y0, double obj_out[4]);
 
 /* LISI, the integration metric of the reference (harmonypy/lisi.py:24-133 `compute_lisi` +
- * `compute_simpson`), on the device.  X: n x d row-major float64 (host).  label_codes: n_labels x n
+ * `compute_simpson`), on the device.  X: n x d row-major float64 (host), d in [1, HMX_MAX_PCS]; for X already
+ * in device memory see hmx_device_io.h, hmx_compute_lisi_device.  label_codes: n_labels x n
  * category codes (one row per label column, as pd.Categorical(...).codes).  perplexity: as the
  * reference's; the search asks for int(3*perplexity) neighbours (the cell itself included, then
  * dropped, lisi.py:53-60), at most 2040 (perplexity 680).  lisi_out: n x n_labels row-major float64 (-1 where the

@@ -12,7 +12,7 @@
 extern "C" {
 #endif
 
-/* Element types of a caller's device tensor (hmx_upload_device). */
+/* Element types of a caller's device tensor (hmx_upload_device, hmx_compute_lisi_device). */
 #define HMX_DTYPE_F32 0
 #define HMX_DTYPE_F16 1
 #define HMX_DTYPE_BF16 2
@@ -37,6 +37,18 @@ int hmx_upload_device(hmx_engine* e, const void* Z, int dtype, int64_t stride_ce
  * elements and >= 1; nothing else of dst is written.  Asynchronous: the engine's stream waits for an event recorded on
  * stream (the caller's hipStream_t, NULL = the null stream) before it writes, and stream waits for the copy. */
 int hmx_copy_out_device(hmx_engine* e, int which, void* dst, int64_t stride_cell, int64_t stride_col, void* stream);
+
+/* hmx_compute_lisi of hmx.h with X in device memory of GPU device_id: n cells x d features (d in [1, HMX_MAX_PCS]) of
+ * type dtype (HMX_DTYPE_*), element (cell r, feature c) at X + r * stride_cell + c * stride_col, strides in elements,
+ * any non-negative values (row-major, .T of a d x n tensor, column slices, row-strided views).  Every element is
+ * converted to float64 exactly, so the results equal hmx_compute_lisi's on the same values.  label_codes stays in
+ * HOST memory (n_labels x n, as for hmx_compute_lisi).  lisi_out (n x n_labels float64) and knn_dist_out / knn_idx_out
+ * (n x (nn-1) float64 / int32, both or neither, may be NULL) are DEVICE pointers of that GPU, row-major, written by the
+ * kernels in place.  stream: the caller's hipStream_t (NULL = the null stream); the work runs there, behind what was
+ * queued before it, and the call returns once it has completed. */
+int hmx_compute_lisi_device(int32_t device_id, const void* X, int dtype, int64_t n, int32_t d, int64_t stride_cell,
+                            int64_t stride_col, void* stream, const int32_t* label_codes, int32_t n_labels, double perplexity,
+                            double* lisi_out, double* knn_dist_out, int32_t* knn_idx_out);
 
 #ifdef __cplusplus
 }
