@@ -4,11 +4,13 @@ Drop-in for the hot path of slowkow/harmonypy: ``run_harmony`` / ``Harmony`` kee
 reference's signatures (harmonypy/__init__.py:1-4, harmony.py:49-67, 218-229); the
 ``harmonize()`` loop runs as hand-written HIP kernels for gfx950 behind a C ABI
 (include/hmx.h, harmonypy_amd/libhmx.so).  ``compute_lisi`` (lisi.py:24-66) is the
-reference's integration metric on the same device.
+reference's integration metric on the same device.  ``map_query`` places new cells onto a finished reference
+(``HarmonyReference``) without a new run.
 """
 from .harmony import Harmony, run_harmony, BatchCodes  # noqa: F401
 from .dist import Shard  # noqa: F401
 from .lisi import compute_lisi  # noqa: F401
+from .mapping import HarmonyReference, map_query  # noqa: F401
 
 __version__ = "0.3.0"
 
@@ -21,4 +23,4 @@ def engine_version() -> str:
     return _capi.build_id()
 
 
-__all__ = ["Harmony", "run_harmony", "BatchCodes", "Shard", "compute_lisi", "__version__", "engine_version"]
+__all__ = ["Harmony", "run_harmony", "BatchCodes", "Shard", "compute_lisi", "map_query", "HarmonyReference", "__version__", "engine_version"]

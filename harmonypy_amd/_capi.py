@@ -1,4 +1,4 @@
-"""ctypes binding of libhmx.so (include/hmx.h, include/hmx_device_io.h).  Thin: argument marshalling and error text only.
+"""ctypes binding of libhmx.so (include/hmx.h, include/hmx_device_io.h, include/hmx_map.h).  Thin: argument marshalling and error text only.
 
 The library is the product's compute path; there is no fallback.  Importing this module
 without a built ``libhmx.so`` raises, and every entry point raises ``HmxError`` with the
@@ -31,6 +31,8 @@ EXPORTS = [
 ]
 # include/hmx_device_io.h: the device I/O path (same ABI version; its own header, see there)
 DEVICE_IO_EXPORTS = ["hmx_upload_device", "hmx_copy_out_device", "hmx_compute_lisi_device"]
+# include/hmx_map.h: reference mapping (same ABI version; its own header)
+MAP_EXPORTS = ["hmx_reference_summary", "hmx_map_query"]
 HMX_PEER_HANDLE_BYTES = 64
 HMX_ABI_VERSION = 8
 HMX_UNIQUE_ID_BYTES = 128
@@ -108,7 +110,9 @@ def load():
     lib.hmx_enable_timing.argtypes = [vp, C.c_int]
     lib.hmx_set_timing_stride.argtypes = [vp, C.c_int]
     lib.hmx_set_timing_families.argtypes = [vp, C.c_uint]
-    for name in EXPORTS + DEVICE_IO_EXPORTS:
+    lib.hmx_reference_summary.argtypes = [vp, vp, vp]
+    lib.hmx_map_query.argtypes = [vp, vp, vp]
+    for name in EXPORTS + DEVICE_IO_EXPORTS + MAP_EXPORTS:
         if name not in ("hmx_last_error", "hmx_destroy", "hmx_build_id"):
             getattr(lib, name).restype = C.c_int
     lib.hmx_build_id.restype = C.c_char_p
@@ -302,6 +306,22 @@ class Engine:
 
     def moe_correct_ridge(self):
         _check(self._lib.hmx_moe_correct_ridge(self._h))
+
+    def reference_summary(self):
+        """(cluster_sums K x d, cluster_mass K), float64: R^T.Z_corr and R's cluster masses of the current state, summed
+        over ranks (hmx_reference_summary)."""
+        sums = np.empty((self.K, self.d), np.float64)
+        mass = np.empty(self.K, np.float64)
+        _check(self._lib.hmx_reference_summary(self._h, _ptr(sums), _ptr(mass)))
+        return sums, mass
+
+    def map_query(self, cluster_sums, cluster_mass):
+        """Assign the uploaded query to the reference's centroids and correct it with the reference in the intercept
+        (hmx_map_query): R, O, T, Z_corr and Z_cos are the query's afterwards."""
+        sums = _c(cluster_sums, np.float64)
+        mass = _c(cluster_mass, np.float64)
+        assert sums.shape == (self.K, self.d) and mass.shape == (self.K,)
+        _check(self._lib.hmx_map_query(self._h, _ptr(sums), _ptr(mass)))
 
     _SHAPES = {
         HMX_Z_ORIG: ("N", "d", np.float32), HMX_Z_COS: ("N", "d", np.float32), HMX_Z_CORR: ("N", "d", np.float32),

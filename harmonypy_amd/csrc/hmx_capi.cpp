@@ -15,6 +15,7 @@
 
 #include "hmx.h"
 #include "hmx_device_io.h"
+#include "hmx_map.h"
 #include "hmx_internal.h"
 #ifdef RTZ_PROF
 void rtz_prof_dump();
@@ -106,6 +107,7 @@ struct hmx_engine {
     uint64_t seeded_rounds = 0;
     int64_t Ng = 0;              // cells of the whole job (all ranks)
     DevBuf<double> Ogrp, Tmass, Ohist, scratch;
+    DevBuf<double> ref_terms;    // hmx_map_query: the reference's cluster masses (K16) then sums (K16 x ldy), zero padded
     // Tables that are summed over ranks live in one allocation, laid out so that tables summed at the
     // same point of the algorithm are neighbours (one collective each):
     //   Sold [nblk][G][K16] | Yacc64 [K16][ldy] | Snew [nblk][G][K16] | objacc [2*SLOTS+2] | Sr [G][K16][ldy] | Oxr [G][K16]
@@ -437,7 +439,7 @@ int hmx_create(const hmx_config* cfg, hmx_engine** out) {
         if (se != hipSuccess) { rc = fail(HMX_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(se)); break; }
         const size_t N = (size_t)e->N, GK = (size_t)e->G * e->K16, GKs = GK + e->K16;
         // + 16 rows of slack behind Z_orig / Z_cos / R: the streaming pass (k_rtz3) fetches whole 16-cell tiles
-        if ((rc = e->Zorig.reserve((N + 16) * e->dp)) || (rc = e->Zcos.reserve((N + 16) * e->dp)) || (rc = e->Zcorr.reserve(N * e->dp)) ||
+        if ((rc = e->Zorig.reserve((N + 16) * e->dp)) || (rc = e->Zcos.reserve((N + 16) * e->dp)) || (rc = e->Zcorr.reserve((N + 16) * e->dp)) ||
             (rc = e->R.reserve((N + 16) * e->Kp + e->K16 + 64)) || (rc = e->Osave.reserve(GK)) || (rc = e->Y.reserve((size_t)e->K16 * e->ldy)) ||
             (rc = e->Yacc.reserve((size_t)e->K16 * e->ldy)) || (rc = e->sigma.reserve(e->K16)) ||
             (rc = e->theta.reserve(e->B)) || (rc = e->Pr_b.reserve(e->B)) || (rc = e->lamb.reserve(e->B + 1)) ||
@@ -506,7 +508,7 @@ void hmx_destroy(hmx_engine* e) {
     e->t3_t0.release(); e->t3_t1.release(); e->t3_stride.release(); e->t3_c0.release(); e->t3_cend.release(); e->t3_grp.release(); e->s_tile_start.release();
     e->tile_blk[0].release(); e->tile_blk[1].release(); e->tile_blk_zero.release(); e->Osave.release(); e->Opriv.release(); e->Wf.release(); e->Yf.release(); e->Zcf.release();
     e->task_grp.release(); e->gstart.release(); e->chunk_tab.release(); e->run_count.release(); e->run_start.release();
-    e->Ogrp.release(); e->Tmass.release(); e->Ohist.release(); e->xch.release(); e->scratch.release();
+    e->Ogrp.release(); e->ref_terms.release(); e->Tmass.release(); e->Ohist.release(); e->xch.release(); e->scratch.release();
     e->cell_map.release(); e->cell_inv.release();
     for (auto ev : e->io_ev) if (ev) (void)hipEventDestroy(ev);
     e->global_id.release(); e->wait_stats.release(); e->sync_words.p = nullptr; e->sync_words.n = 0; e->Sslots.release(); e->km_hn.release(); e->km_sums.release();
@@ -759,6 +761,7 @@ int upload_impl(hmx_engine* e, const ZSource& z, const int32_t* static_cells, in
             HIP_TRY(hipMemsetAsync(e->R.p + (size_t)e->N * e->Kp, 0, (size_t)16 * e->Kp * sizeof(float), e->stream));
             HIP_TRY(hipMemsetAsync(e->Zorig.p + (size_t)e->N * e->dp, 0, (size_t)16 * e->dp * sizeof(float), e->stream));
             HIP_TRY(hipMemsetAsync(e->Zcos.p + (size_t)e->N * e->dp, 0, (size_t)16 * e->dp * sizeof(float), e->stream));
+            HIP_TRY(hipMemsetAsync(e->Zcorr.p + (size_t)e->N * e->dp, 0, (size_t)16 * e->dp * sizeof(float), e->stream));   // (hmx_reference_summary)
             HIP_TRY(hipStreamSynchronize(e->stream));
         }
     }
@@ -1072,9 +1075,11 @@ struct Rtz3Duties { bool on = false; };
 // The R^T.Z pass in storage order (k_rtz3 + k_rtz3_finish).
 //   mode 0: Z_cos; block ids `tile_blk` with `nblk_cols` one-hot columns -> Yacc64 (centroid numerators, :443),
 //           Sold (removal sums of every block, :491-492) and, with `normalize`, Y (:444);
-//   mode 1: Z_orig, all ids 0 -> Sr (ridge right-hand sides, :556-563), Oxr (exact O, :550);
+//   mode 1: Z_orig (or `z1`: Z_corr for the reference summary), all ids 0 -> Sr (ridge right-hand sides, :556-563),
+//           Oxr (exact O, :550);
 //   mode 2: the same statistics of Z_cos (member sums and counts of the device k-means' hard assignment).
-static int rtz3_pass(hmx_engine* e, int mode, const unsigned char* tile_blk, int nblk_cols, bool normalize, bool duties) {
+static int rtz3_pass(hmx_engine* e, int mode, const unsigned char* tile_blk, int nblk_cols, bool normalize, bool duties,
+                     const float* z1 = nullptr) {
     int rc;
     const bool wide = !(use_rtz3(e) && rtz3_ok(e->mt, e->dp, nblk_cols, e->G));   // (mode 2 comes here for wide shapes whatever the rounds' kernel is)
     if ((rc = e->slab.reserve((size_t)e->ntasks3 * (wide ? rtzw_slab_floats(e->mt, e->dp, e->d, nblk_cols) : rtz3_slab_floats(e->mt, e->dp, nblk_cols)))))
@@ -1082,7 +1087,7 @@ static int rtz3_pass(hmx_engine* e, int mode, const unsigned char* tile_blk, int
     {
         Timed t(e, mode == 1 ? F_RIDGE_STATS : F_RTZ_ROUND);
         Rtz3Args r{};
-        r.R = e->R.p; r.Z = mode == 1 ? e->Zorig.p : e->Zcos.p; r.tile_blk = tile_blk;
+        r.R = e->R.p; r.Z = mode == 1 ? (z1 ? z1 : e->Zorig.p) : e->Zcos.p; r.tile_blk = tile_blk;
         r.task_t0 = e->t3_t0.p; r.task_t1 = e->t3_t1.p; r.task_stride = e->t3_stride.p; r.task_c0 = e->t3_c0.p; r.task_cend = e->t3_cend.p;
         r.slab = e->slab.p; r.ntasks = e->ntasks3; r.Kp = e->Kp;
         r.frozen = duties ? e->frozen() : nullptr;   // (the fused round of a single engine: the only path whose read-back is deferred)
@@ -1990,11 +1995,11 @@ int hmx_set_host_allreduce(hmx_engine* e, hmx_host_allreduce_fn fn, void* ctx) {
     return HMX_OK;
 }
 
-int hmx_moe_correct_ridge(hmx_engine* e) {
-    if (!e) return fail(HMX_ERR_ARG, "null argument");
-    if (!e->clustered) return fail(HMX_ERR_STATE, "no soft assignment yet");
+// The ridge statistics of harmony.py:550, 556-563 over the cells' rows of `Z` (Z_orig for the ridge, Z_corr for the
+// reference summary): Sr (G x K16 x ldy, sum_i R_ki z_i per batch group) and Oxr (G x K16, sum_i R_ki per group), summed
+// over ranks.  The streaming pass (rtz3_pass mode 1) or the list-order kernels k_rtz2 / k_rtz_wide / k_rtz.
+static int ridge_stats(hmx_engine* e, const float* Z) {
     int rc;
-    if ((rc = use_device(e))) return rc;
     const size_t GK = (size_t)e->G * e->K16;
     int nsub, spw;
     rtz_geometry(e->mt, e->ntd, &nsub, &spw);
@@ -2005,14 +2010,14 @@ int hmx_moe_correct_ridge(hmx_engine* e) {
         return rc;
     if (streaming_rtz(e)) {
         // the streaming pass: Sr and Oxr are written whole by k_rtz3_finish (no fills)
-        if ((rc = rtz3_pass(e, 1, e->tile_blk_zero.p, 1, false, false))) return rc;
+        if ((rc = rtz3_pass(e, 1, e->tile_blk_zero.p, 1, false, false, Z))) return rc;
     } else {
     HIP_TRY(hipMemsetAsync(e->Sr, 0, GK * e->ldy * sizeof(double), e->stream));
     HIP_TRY(hipMemsetAsync(e->Oxr, 0, GK * sizeof(double), e->stream));
     {
         Timed t(e, F_RIDGE_STATS);
         RtzArgs r{};
-        r.R = e->R.p; r.Z = e->Zorig.p; r.cells = e->s_cells.p; r.tile_grp = e->s_tile_grp.p;
+        r.R = e->R.p; r.Z = Z; r.cells = e->s_cells.p; r.tile_grp = e->s_tile_grp.p;
         r.task_tile0 = e->task_t0.p; r.task_tile1 = e->task_t1.p; r.task_grp = e->task_grp.p;
         r.S_out = e->Oxr; r.slab = e->slab.p; r.n_tiles = e->n_s_tiles; r.ntasks = e->ntasks;
         r.K = e->K; r.Kp = e->Kp; r.K16 = e->K16; r.G = e->G; r.mt = e->mt; r.dp = e->dp; r.ntd = e->ntd;
@@ -2028,12 +2033,21 @@ int hmx_moe_correct_ridge(hmx_engine* e) {
         }
     }
     }
-    if ((rc = sum_over_ranks(e, e->Sr, GK * e->ldy + GK))) return rc;   // Sr and Oxr are neighbours
+    return sum_over_ranks(e, e->Sr, GK * e->ldy + GK);   // Sr and Oxr are neighbours
+}
+
+// harmony.py:541-569 from the statistics of ridge_stats: the per-cluster solve, then Z_corr = Z_orig - sum_k W_k^T Phi_k
+// and Z_cos.  ref_mass / ref_sums (device, K16 and K16 x ldy): the reference terms of hmx_map_query, or null.
+static int ridge_solve_apply(hmx_engine* e, const double* ref_mass, const double* ref_sums) {
+    int rc;
+    const bool rtz2 = rtz2_ok(e->mt, e->dp);
+    const bool rtzw = !rtz2 && rtz_wide_ok(e->mt, e->dp);
     {
         Timed t(e, F_RIDGE_SOLVE);
         RidgeSolveArgs s{};
         s.S = e->Sr; s.Ox = e->Oxr; s.T = e->Tmass.p; s.lamb = e->lamb.p; s.Pr_b = e->Pr_b.p; s.group_cols = e->group_cols.p;
         s.W = e->W.p; s.scratch = e->scratch.p; s.alpha = e->cfg.alpha; s.lambda_est = e->cfg.lambda_estimation;
+        s.ref_mass = ref_mass; s.ref_sums = ref_sums;
         s.K = e->K; s.K16 = e->K16; s.G = e->G; s.B = e->B; s.V = e->V; s.d = e->d; s.lds = e->ldy; s.ldw = e->ldy;
         launch_ridge_solve(s, e->stream);
     }
@@ -2052,6 +2066,81 @@ int hmx_moe_correct_ridge(hmx_engine* e) {
         }
         if (launch_ridge_apply(a, e->max_wgs, e->stream)) return fail(HMX_ERR_ARG, "unsupported n_pcs");
     }
+    HIP_TRY(hipGetLastError());
+    return HMX_OK;
+}
+
+int hmx_moe_correct_ridge(hmx_engine* e) {
+    if (!e) return fail(HMX_ERR_ARG, "null argument");
+    if (!e->clustered) return fail(HMX_ERR_STATE, "no soft assignment yet");
+    int rc;
+    if ((rc = use_device(e))) return rc;
+    if ((rc = ridge_stats(e, e->Zorig.p))) return rc;
+    return ridge_solve_apply(e, nullptr, nullptr);
+}
+
+// ---- reference mapping (include/hmx_map.h) ------------------------------------------------------
+
+int hmx_reference_summary(hmx_engine* e, double* cluster_sums_out, double* cluster_mass_out) {
+    if (!e || !cluster_sums_out || !cluster_mass_out) return fail(HMX_ERR_ARG, "null argument");
+    if (!e->uploaded) return fail(HMX_ERR_STATE, "hmx_upload must come first");
+    if (!e->clustered) return fail(HMX_ERR_STATE, "hmx_reference_summary: no soft assignment yet");
+    int rc;
+    if ((rc = use_device(e))) return rc;
+    if ((rc = ridge_stats(e, e->Zcorr.p))) return rc;   // Sr / Oxr of Z_corr: per group, summed over ranks
+    const size_t GK = (size_t)e->G * e->K16, n = GK * e->ldy + GK;
+    std::vector<double> h(n);
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(h.data(), e->Sr, n * sizeof(double), hipMemcpyDeviceToHost));
+    const double* S = h.data();
+    const double* O = S + GK * e->ldy;
+    for (int k = 0; k < e->K; ++k) {
+        double m = 0.0;
+        for (int g = 0; g < e->G; ++g) m += O[(size_t)g * e->K16 + k];
+        cluster_mass_out[k] = m;
+        for (int j = 0; j < e->d; ++j) {
+            double v = 0.0;
+            for (int g = 0; g < e->G; ++g) v += S[((size_t)g * e->K16 + k) * e->ldy + j];
+            cluster_sums_out[(size_t)k * e->d + j] = v;
+        }
+    }
+    return HMX_OK;
+}
+
+int hmx_map_query(hmx_engine* e, const double* cluster_sums, const double* cluster_mass) {
+    if (!e || !cluster_sums || !cluster_mass) return fail(HMX_ERR_ARG, "null argument");
+    if (!e->uploaded) return fail(HMX_ERR_STATE, "hmx_upload must come first");
+    const int K = e->K, d = e->d, ldy = e->ldy, K16 = e->K16;
+    std::vector<float> y0((size_t)K * d);
+    std::vector<double> terms((size_t)K16 * (ldy + 1), 0.0);   // masses | sums, the solve's layout
+    for (int k = 0; k < K; ++k) {
+        const double m = cluster_mass[k];
+        if (!std::isfinite(m)) return fail(HMX_ERR_ARG, "hmx_map_query: cluster_mass[%d] is not finite", k);
+        terms[k] = m;
+        double ss = 0.0;
+        for (int j = 0; j < d; ++j) {
+            const double v = cluster_sums[(size_t)k * d + j];
+            if (!std::isfinite(v)) return fail(HMX_ERR_ARG, "hmx_map_query: cluster_sums[%d][%d] is not finite", k, j);
+            ss += v * v;
+            terms[K16 + (size_t)k * ldy + j] = v;
+            y0[(size_t)k * d + j] = (float)v;
+        }
+        if (!(ss > 0.0)) return fail(HMX_ERR_ARG, "hmx_map_query: cluster_sums[%d] is zero (no centroid direction)", k);
+    }
+    int rc;
+    if ((rc = use_device(e))) return rc;
+    // 1-2: centroids = the sums at unit length, and the init assignment against them (R, O, T; harmony.py:376-389)
+    double obj[4];
+    if ((rc = hmx_init_cluster(e, y0.data(), obj))) return rc;
+    // 3: the ridge statistics of the query (harmony.py:550, 556-563)
+    if ((rc = ridge_stats(e, e->Zorig.p))) return rc;
+    // 4-5: the solve with the reference terms, the apply (Z_corr, Z_cos)
+    if ((rc = e->ref_terms.reserve(terms.size()))) return rc;
+    HIP_TRY(hipMemcpyAsync(e->ref_terms.p, terms.data(), terms.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    rc = ridge_solve_apply(e, e->ref_terms.p, e->ref_terms.p + K16);
+    HIP_TRY(hipStreamSynchronize(e->stream));   // (terms is read by the copy above)
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
     return HMX_OK;
 }

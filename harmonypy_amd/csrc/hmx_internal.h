@@ -186,6 +186,8 @@ struct RidgeSolveArgs {
     const int* group_cols;
     float* W;              // G x K16 x ldw
     double* scratch;       // general path: K16 x (B+1) x (B+1+d)
+    const double* ref_mass;  // reference mapping (hmx_map_query): K16 cluster masses added to the intercept pivot, or null
+    const double* ref_sums;  // ... K16 x lds cluster sums added to the intercept right-hand side, or null
     float alpha;
     int lambda_est;
     int K, K16, G, B, V, d, lds, ldw;

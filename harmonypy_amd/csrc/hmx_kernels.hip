@@ -3576,6 +3576,8 @@ __global__ __launch_bounds__(256) void k_group_sums(const float* __restrict__ R,
 //     w_0 = (sum_b c_b S_b) / (lambda_0 + sum_b c_b O_b)
 //     w_b = (S_b - O_b w_0) / (O_b + lambda_b)
 // evaluated in fp64 (cancellation-free form).  Row 0 is dropped (harmony.py:565).
+// Reference mapping (ref_mass / ref_sums non-null, hmx_map_query): the reference's cluster mass m_k and sums s_k enter the
+// intercept row only, so w_0 = (sum_b c_b S_b + s_k) / (lambda_0 + m_k + sum_b c_b O_b) and w_b keeps its form.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void k_ridge_solve_v1(RidgeSolveArgs a) {
     const int k = blockIdx.x;
@@ -3590,6 +3592,10 @@ __global__ __launch_bounds__(64) void k_ridge_solve_v1(RidgeSolveArgs a) {
                 const double c = lam / (O + lam);
                 num += c * a.S[((size_t)b * a.K16 + k) * a.lds + j];
                 den += c * O;
+            }
+            if (a.ref_mass) {
+                num += a.ref_sums[(size_t)k * a.lds + j];
+                den += a.ref_mass[k];
             }
         }
         const double w0 = (j < a.d && k < a.K) ? num / den : 0.0;
@@ -3610,6 +3616,7 @@ __global__ __launch_bounds__(64) void k_ridge_solve_v1(RidgeSolveArgs a) {
 // One workgroup per cluster.  Group tables -> column tables:
 //   cov[0][0] = sum_g Ox[g] + lambda_0, cov[0][b+1] = Ocol[b], cov[b+1][c+1] = sum_{g has b,c} Ox[g]
 //   rhs[0] = sum_g S_g, rhs[b+1] = sum_{g has b} S_g;   W_eff[g] = sum_v w[col(g,v)+1]
+// Reference mapping (ref_mass / ref_sums non-null): cov[0][0] += m_k, rhs[0] += s_k.
 __global__ __launch_bounds__(256) void k_ridge_solve_general(RidgeSolveArgs a) {
     const int k = blockIdx.x;
     const int tid = threadIdx.x;
@@ -3646,6 +3653,10 @@ __global__ __launch_bounds__(256) void k_ridge_solve_general(RidgeSolveArgs a) {
         }
         __threadfence_block();
         __syncthreads();
+    }
+    if (a.ref_mass) {
+        if (tid == 0) M[0] += a.ref_mass[k];
+        for (int j = tid; j < a.d; j += blockDim.x) M[n + j] += a.ref_sums[(size_t)k * a.lds + j];
     }
     for (int b = tid; b < n; b += blockDim.x) {
         double lam;

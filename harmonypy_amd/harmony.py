@@ -431,7 +431,94 @@ def build_block_lists(update_order, rank, gid_int, n_blocks, cells_per_block, G,
     return cells, tile_grp, blk_start
 
 
-class Harmony:
+class _EngineArrays:
+    """What ``Harmony`` and ``mapping.HarmonyQuery`` share: an engine (``_engine``) over N cells stored group-sorted
+    (``_order``: internal row -> the caller's row), its upload and the read-back of the N-sized arrays."""
+
+    def _upload(self, Z, lamb):
+        """Z (d x N: a host array or a device tensor view) and the batch layout into the engine; returns the name of the
+        path taken ("upload_device" / "upload")."""
+        # a cell's id in the whole job = its row in the unsharded input
+        src = self._order.astype(np.int32)
+        gid = src if self._offset == 0 else (self._offset + self._order).astype(np.int32)
+        if not isinstance(Z, np.ndarray):
+            # a device tensor (d x N view): the engine reads it in place, in its dtype and strides, ordered behind the
+            # work queued on the caller's current stream; same regrouping and ids as below
+            import torch
+            self._engine.upload_device(Z.data_ptr(), _device_dtype(Z), Z.stride(1), Z.stride(0),
+                                       torch.cuda.current_stream(Z.device).cuda_stream,
+                                       self._static_cells, self._static_tile_grp, self._group_cols, self._Pr_b,
+                                       self._theta, self._sigma, lamb, global_id=gid, source_row=src)
+            return "upload_device"
+        # Z travels cells x d in the caller's order; the device regroups it (source_row)
+        self._engine.upload(np.ascontiguousarray(Z.T), self._static_cells, self._static_tile_grp,
+                            self._group_cols, self._Pr_b, self._theta, self._sigma, lamb, global_id=gid, source_row=src)
+        return "upload"
+
+    # ------------------------------------------------------------------
+    # read-back (harmony.py:288-355): fresh float32 NumPy arrays, cells x features
+    # ------------------------------------------------------------------
+    def _rows(self, which):
+        out = self._engine.get(which)
+        res = np.empty_like(out)
+        res[self._order] = out                    # internal (group-sorted) rows back to the caller's order
+        return res
+
+    _DEVICE_ARRAYS = {"Z_corr": _capi.HMX_Z_CORR, "Z_orig": _capi.HMX_Z_ORIG, "Z_cos": _capi.HMX_Z_COS, "R": _capi.HMX_R}
+
+    def to_tensor(self, which="Z_corr", out=None):
+        """``Z_corr`` / ``Z_orig`` / ``Z_cos`` / ``R`` as a float32 torch tensor on the engine's device: cells x
+        features in the caller's cell order, the same values as the NumPy property, without a trip through the host.
+
+        ``out``: a float32 tensor of that shape on that device, any strides (a d x N view, a column slice of a wider
+        matrix); written in place, nothing outside the view is touched.  The copy is ordered on the current stream."""
+        import torch
+        if which not in self._DEVICE_ARRAYS:
+            raise ValueError(f"which={which!r}: expected one of {sorted(self._DEVICE_ARRAYS)}")
+        shape = (self.N, self.K if which == "R" else self.d)
+        dev = torch.device("cuda", self._device_id)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=dev)
+        else:
+            if not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.float32:
+                raise ValueError(f"out must be a float32 tensor on {dev}")
+            if tuple(out.shape) != shape:
+                raise ValueError(f"out has shape {tuple(out.shape)}, {which} is {shape}")
+            if any(st < 1 and n > 1 for st, n in zip(out.stride(), out.shape)):
+                raise ValueError("out must not overlap itself (a stride of 0)")
+        # a dimension of one element may carry any stride: give the library a valid one
+        sc, sf = (st if n > 1 else 1 for st, n in zip(out.stride(), out.shape))
+        self._engine.copy_out_device(self._DEVICE_ARRAYS[which], out.data_ptr(), sc, sf,
+                                     torch.cuda.current_stream(dev).cuda_stream)
+        return out
+
+    @property
+    def Z_corr(self):
+        """Corrected embedding (N x d)."""
+        return self._rows(_capi.HMX_Z_CORR)
+
+    @property
+    def Z_orig(self):
+        """Input embedding (N x d)."""
+        return self._rows(_capi.HMX_Z_ORIG)
+
+    @property
+    def Z_cos(self):
+        """L2-normalised embedding used for clustering (N x d)."""
+        return self._rows(_capi.HMX_Z_COS)
+
+    @property
+    def R(self):
+        """Soft cluster assignment (N x K)."""
+        return self._rows(_capi.HMX_R)
+
+    @property
+    def Y(self):
+        """Unit-length cluster centroids (d x K)."""
+        return np.ascontiguousarray(self._engine.get(_capi.HMX_Y).T)
+
+
+class Harmony(_EngineArrays):
     """Device-resident Harmony state with the reference's object API (harmony.py:218-569).
 
     ``Z`` is d x N (PCs x cells) like the reference's -- a host array, or a tensor on a HIP device
@@ -547,64 +634,8 @@ class Harmony:
                                     device_id=self._device_id, n_cells_global=self.N_global)
         self.transport = None if self.shard is None else self.shard.attach(self._engine)
         self._lap("engine_create")
-        if Z is not None and not isinstance(Z, np.ndarray):
-            # a device tensor (d x N view): the engine reads it in place, in its dtype and strides, ordered behind the
-            # work queued on the caller's current stream; same regrouping and ids as below
-            import torch
-            src = self._order.astype(np.int32)
-            gid = src if self._offset == 0 else (self._offset + self._order).astype(np.int32)
-            self._engine.upload_device(Z.data_ptr(), _device_dtype(Z), Z.stride(1), Z.stride(0),
-                                       torch.cuda.current_stream(Z.device).cuda_stream,
-                                       self._static_cells, self._static_tile_grp, self._group_cols, self._Pr_b,
-                                       self._theta, self._sigma, None if self.lambda_estimation else self._lamb,
-                                       global_id=gid, source_row=src)
-            self._lap("upload_device")
-        elif Z is not None:
-            # Z travels cells x d in the caller's order; the device regroups it (source_row).
-            # A cell's id in the whole job = its row in the unsharded input.
-            src = self._order.astype(np.int32)
-            gid = src if self._offset == 0 else (self._offset + self._order).astype(np.int32)
-            self._engine.upload(np.ascontiguousarray(Z.T), self._static_cells, self._static_tile_grp,
-                                self._group_cols, self._Pr_b, self._theta, self._sigma,
-                                None if self.lambda_estimation else self._lamb, global_id=gid, source_row=src)
-            self._lap("upload")
-
-    # ------------------------------------------------------------------
-    # read-back (harmony.py:288-355): fresh float32 NumPy arrays, cells x features
-    # ------------------------------------------------------------------
-    def _rows(self, which):
-        out = self._engine.get(which)
-        res = np.empty_like(out)
-        res[self._order] = out                    # internal (group-sorted) rows back to the caller's order
-        return res
-
-    _DEVICE_ARRAYS = {"Z_corr": _capi.HMX_Z_CORR, "Z_orig": _capi.HMX_Z_ORIG, "Z_cos": _capi.HMX_Z_COS, "R": _capi.HMX_R}
-
-    def to_tensor(self, which="Z_corr", out=None):
-        """``Z_corr`` / ``Z_orig`` / ``Z_cos`` / ``R`` as a float32 torch tensor on the engine's device: cells x
-        features in the caller's cell order, the same values as the NumPy property, without a trip through the host.
-
-        ``out``: a float32 tensor of that shape on that device, any strides (a d x N view, a column slice of a wider
-        matrix); written in place, nothing outside the view is touched.  The copy is ordered on the current stream."""
-        import torch
-        if which not in self._DEVICE_ARRAYS:
-            raise ValueError(f"which={which!r}: expected one of {sorted(self._DEVICE_ARRAYS)}")
-        shape = (self.N, self.K if which == "R" else self.d)
-        dev = torch.device("cuda", self._device_id)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=dev)
-        else:
-            if not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.float32:
-                raise ValueError(f"out must be a float32 tensor on {dev}")
-            if tuple(out.shape) != shape:
-                raise ValueError(f"out has shape {tuple(out.shape)}, {which} is {shape}")
-            if any(st < 1 and n > 1 for st, n in zip(out.stride(), out.shape)):
-                raise ValueError("out must not overlap itself (a stride of 0)")
-        # a dimension of one element may carry any stride: give the library a valid one
-        sc, sf = (st if n > 1 else 1 for st, n in zip(out.stride(), out.shape))
-        self._engine.copy_out_device(self._DEVICE_ARRAYS[which], out.data_ptr(), sc, sf,
-                                     torch.cuda.current_stream(dev).cuda_stream)
-        return out
+        if Z is not None:
+            self._lap(self._upload(Z, None if self.lambda_estimation else self._lamb))
 
     @property
     def _rank(self):
@@ -612,31 +643,6 @@ class Harmony:
         if self._rank_cache is None:
             self._rank_cache = inverse_order(self._order)
         return self._rank_cache
-
-    @property
-    def Z_corr(self):
-        """Corrected embedding (N x d)."""
-        return self._rows(_capi.HMX_Z_CORR)
-
-    @property
-    def Z_orig(self):
-        """Input embedding (N x d)."""
-        return self._rows(_capi.HMX_Z_ORIG)
-
-    @property
-    def Z_cos(self):
-        """L2-normalised embedding used for clustering (N x d)."""
-        return self._rows(_capi.HMX_Z_COS)
-
-    @property
-    def R(self):
-        """Soft cluster assignment (N x K)."""
-        return self._rows(_capi.HMX_R)
-
-    @property
-    def Y(self):
-        """Unit-length cluster centroids (d x K)."""
-        return np.ascontiguousarray(self._engine.get(_capi.HMX_Y).T)
 
     @property
     def O(self):
@@ -682,6 +688,14 @@ class Harmony:
     def result(self):
         """Corrected data as a NumPy array (N x d), harmony.py:353-355."""
         return self.Z_corr
+
+    def reference(self):
+        """The summary that ``harmonypy_amd.map_query`` maps new cells onto: ``HarmonyReference`` with the cluster masses
+        and ``R^T . Z_corr`` of the current state (computed on the device, over all ranks of a sharded job -- every rank
+        must call), this object's sigma and ``n_cells = N_global``.  The state itself is not changed."""
+        from .mapping import HarmonyReference
+        sums, mass = self._engine.reference_summary()
+        return HarmonyReference(sums, mass, self._sigma, self.N_global)
 
     # ------------------------------------------------------------------
     # harmony.py:366-392
