@@ -1,4 +1,4 @@
-"""ctypes binding of libhmx.so (include/hmx.h, include/hmx_device_io.h, include/hmx_map.h).  Thin: argument marshalling and error text only.
+"""ctypes binding of libhmx.so (include/hmx.h, include/hmx_device_io.h, include/hmx_map.h, include/hmx_knn.h).  Thin: argument marshalling and error text only.
 
 The library is the product's compute path; there is no fallback.  Importing this module
 without a built ``libhmx.so`` raises, and every entry point raises ``HmxError`` with the
@@ -33,6 +33,8 @@ EXPORTS = [
 DEVICE_IO_EXPORTS = ["hmx_upload_device", "hmx_copy_out_device", "hmx_compute_lisi_device"]
 # include/hmx_map.h: reference mapping (same ABI version; its own header)
 MAP_EXPORTS = ["hmx_reference_summary", "hmx_map_query"]
+# include/hmx_knn.h: cross-set kNN and label vote (same ABI version; its own header)
+KNN_EXPORTS = ["hmx_knn_predict", "hmx_knn_slices"]
 HMX_PEER_HANDLE_BYTES = 64
 HMX_ABI_VERSION = 8
 HMX_UNIQUE_ID_BYTES = 128
@@ -112,7 +114,10 @@ def load():
     lib.hmx_set_timing_families.argtypes = [vp, C.c_uint]
     lib.hmx_reference_summary.argtypes = [vp, vp, vp]
     lib.hmx_map_query.argtypes = [vp, vp, vp]
-    for name in EXPORTS + DEVICE_IO_EXPORTS + MAP_EXPORTS:
+    lib.hmx_knn_predict.argtypes = [i32, vp, C.c_int, i64, i64, i64, vp, C.c_int, i64, i64, i64, i32, i32, i32, vp, vp, i32,
+                                    vp, vp, vp, vp]
+    lib.hmx_knn_slices.argtypes = [i32, i64, i64, i32, i32]
+    for name in EXPORTS + DEVICE_IO_EXPORTS + MAP_EXPORTS + KNN_EXPORTS:
         if name not in ("hmx_last_error", "hmx_destroy", "hmx_build_id"):
             getattr(lib, name).restype = C.c_int
     lib.hmx_build_id.restype = C.c_char_p

@@ -15,6 +15,7 @@
 
 #include "hmx.h"
 #include "hmx_device_io.h"
+#include "hmx_knn.h"
 #include "hmx_map.h"
 #include "hmx_internal.h"
 #ifdef RTZ_PROF
@@ -932,6 +933,118 @@ int hmx_compute_lisi_device(int32_t device_id, const void* X, int dtype, int64_t
     src.s_col = stride_col;
     src.stream = static_cast<hipStream_t>(stream);
     return lisi_impl(device_id, src, n, d, label_codes, n_labels, perplexity, lisi_out, knn_dist_out, knn_idx_out);
+}
+
+// ---- cross-set kNN and label vote (include/hmx_knn.h) -------------------------------------------------------------
+
+namespace {
+
+constexpr int64_t KNN_MAX_REF = ((int64_t)1 << 31) - 256;        // 32-bit candidate indices, padded rows included
+constexpr int KNN_MAX_SLICES = 65535;                             // the grid's y extent
+constexpr size_t KNN_AUTO_LIST_BYTES = (size_t)4 << 30;           // the automatic choice keeps the slices' lists below this
+
+// Slices the automatic choice cuts the reference into: the fewest whose grid (query blocks x slices) fills at least 90 %
+// of the whole rounds of resident workgroups it takes (one round per n_cus x resident-per-CU workgroups), else the best
+// such fill -- every extra slice repeats the lists' fill-up, a round left mostly empty costs as much as a full one.  Each
+// slice at least 64 tiles (1024 reference cells) long, all lists together below KNN_AUTO_LIST_BYTES.
+int knn_auto_slices(int n_cus, int64_t n_q, int64_t n_r, int dp, int cap) {
+    const int64_t nq_pad = (n_q + 255) & ~(int64_t)255;
+    const int64_t wgs = nq_pad / knn_queries_per_workgroup(dp);
+    const int64_t slots = (int64_t)n_cus * knn_search_workgroups_per_cu(dp, cap);
+    int64_t smax = ((n_r + 15) / 16) / 64;
+    smax = std::min<int64_t>(smax, (int64_t)(KNN_AUTO_LIST_BYTES / ((size_t)nq_pad * cap * sizeof(unsigned long long))));
+    smax = std::max<int64_t>(1, std::min<int64_t>(smax, KNN_MAX_SLICES));
+    int64_t best = 1;
+    double best_fill = 0.0;
+    for (int64_t s = 1; s <= smax; ++s) {
+        const int64_t g = wgs * s, rounds = (g + slots - 1) / slots;
+        const double fill = (double)g / (double)(rounds * slots);
+        if (fill >= 0.9) return (int)s;
+        if (fill > best_fill) { best_fill = fill; best = s; }
+    }
+    return (int)best;
+}
+
+int knn_check_shape(int32_t device_id, int64_t n_q, int64_t n_r, int32_t d, int32_t k, int* cap, int* n_cus) {
+    if (n_q < 1 || n_q > KNN_MAX_REF) return fail(HMX_ERR_ARG, "n_q out of range");
+    if (n_r < 1 || n_r > KNN_MAX_REF) return fail(HMX_ERR_ARG, "n_r must be in [1, %lld]", (long long)KNN_MAX_REF);
+    if (d < 1 || d > HMX_MAX_PCS) return fail(HMX_ERR_ARG, "d must be in [1, %d]", HMX_MAX_PCS);
+    *cap = k >= 1 ? lisi_list_cap(k) : 0;
+    if (*cap == 0) return fail(HMX_ERR_ARG, "k must lie in [1, %d] in this build (got %d)", LISI_MAX_NEIGHBOURS, k);
+    if (k > n_r) return fail(HMX_ERR_ARG, "Expected n_neighbors <= n_samples_fit, but n_neighbors = %d, n_samples_fit = %lld", k, (long long)n_r);
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (device_id < 0 || device_id >= ndev) return fail(HMX_ERR_ARG, "device %d not present (%d devices)", device_id, ndev);
+    HIP_TRY(hipDeviceGetAttribute(n_cus, hipDeviceAttributeMultiprocessorCount, device_id));
+    return HMX_OK;
+}
+
+bool knn_dtype_ok(int t) { return t == HMX_DTYPE_F32 || t == HMX_DTYPE_F16 || t == HMX_DTYPE_BF16 || t == HMX_DTYPE_F64; }
+
+}  // namespace
+
+int hmx_knn_slices(int32_t device_id, int64_t n_q, int64_t n_r, int32_t d, int32_t k) {
+    int cap = 0, n_cus = 0, rc;
+    if ((rc = knn_check_shape(device_id, n_q, n_r, d, k, &cap, &n_cus))) return rc;
+    return knn_auto_slices(n_cus, n_q, n_r, (d + 15) & ~15, cap);
+}
+
+int hmx_knn_predict(int32_t device_id, const void* Q, int q_dtype, int64_t n_q, int64_t q_stride_cell, int64_t q_stride_col,
+                    const void* R, int r_dtype, int64_t n_r, int64_t r_stride_cell, int64_t r_stride_col, int32_t d, int32_t k,
+                    int32_t slices, void* stream, const int32_t* ref_label_codes, int32_t n_labels, int32_t* pred_out,
+                    double* prob_out, double* knn_dist_out, int32_t* knn_idx_out) {
+    if (!Q || !R) return fail(HMX_ERR_ARG, "null argument");
+    if (!knn_dtype_ok(q_dtype) || !knn_dtype_ok(r_dtype)) return fail(HMX_ERR_ARG, "hmx_knn_predict: unknown dtype %d", knn_dtype_ok(q_dtype) ? r_dtype : q_dtype);
+    if (q_stride_cell < 0 || q_stride_col < 0 || r_stride_cell < 0 || r_stride_col < 0) return fail(HMX_ERR_ARG, "hmx_knn_predict: negative stride");
+    if (n_labels < 0) return fail(HMX_ERR_ARG, "n_labels must be >= 0");
+    if ((n_labels > 0) != (ref_label_codes && pred_out && prob_out) || (n_labels == 0 && (ref_label_codes || pred_out || prob_out)))
+        return fail(HMX_ERR_ARG, "ref_label_codes, pred_out and prob_out are given iff n_labels > 0");
+    if ((knn_dist_out == nullptr) != (knn_idx_out == nullptr)) return fail(HMX_ERR_ARG, "knn_dist_out and knn_idx_out go together");
+    if (n_labels == 0 && !knn_dist_out) return fail(HMX_ERR_ARG, "nothing to compute: no labels and no neighbour outputs");
+    if (slices < 0) return fail(HMX_ERR_ARG, "slices must be >= 0 (0 = automatic)");
+    int cap = 0, n_cus = 0, rc;
+    if ((rc = knn_check_shape(device_id, n_q, n_r, d, k, &cap, &n_cus))) return rc;
+    for (int64_t i = 0; i < (int64_t)n_labels * n_r; ++i)
+        if (ref_label_codes[i] < 0) return fail(HMX_ERR_ARG, "ref_label_codes must be >= 0 (label %lld, cell %lld)", (long long)(i / n_r), (long long)(i % n_r));
+    HIP_TRY(hipSetDevice(device_id));
+    const int dp = (d + 15) & ~15;
+    const int64_t nq_pad = (n_q + 255) & ~(int64_t)255, nr_pad = (n_r + 255) & ~(int64_t)255;
+    const int ntiles = (int)((n_r + 15) / 16);
+    int S = slices ? std::min(slices, std::min(ntiles, KNN_MAX_SLICES)) : knn_auto_slices(n_cus, n_q, n_r, dp, cap);
+    const int tps = (ntiles + S - 1) / S;
+    S = (ntiles + tps - 1) / tps;                                                // no empty slice
+    DevBuf<double> Q64, R64, qsums, rsums;
+    DevBuf<float> Q32, R32, cn;
+    DevBuf<unsigned long long> lists;
+    DevBuf<int> counts, labels;
+    struct Release {
+        DevBuf<double>&a, &b, &c, &d2; DevBuf<float>&f, &g, &h; DevBuf<unsigned long long>&i; DevBuf<int>&j, &k2;
+        ~Release() { a.release(); b.release(); c.release(); d2.release(); f.release(); g.release(); h.release(); i.release(); j.release(); k2.release(); }
+    } guard{Q64, R64, qsums, rsums, Q32, R32, cn, lists, counts, labels};
+    if ((rc = Q64.reserve((size_t)n_q * d)) || (rc = R64.reserve((size_t)n_r * d)) || (rc = qsums.reserve(d)) || (rc = rsums.reserve(d)) ||
+        (rc = Q32.reserve((size_t)nq_pad * dp)) || (rc = R32.reserve((size_t)nr_pad * dp)) || (rc = cn.reserve(nr_pad)) ||
+        (rc = lists.reserve((size_t)S * nq_pad * cap)) || (rc = counts.reserve((size_t)S * n_q)) ||
+        (rc = labels.reserve(std::max<size_t>(1, (size_t)n_labels * n_r))))
+        return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n_labels) HIP_TRY(hipMemcpyAsync(labels.p, ref_label_codes, (size_t)n_labels * n_r * sizeof(int), hipMemcpyHostToDevice, s));
+    // both sets centred by the reference's column means (the float32 preselection only; the ranking is on Q64 / R64)
+    launch_knn_load(R, r_dtype, r_stride_cell, r_stride_col, n_r, d, R64.p, rsums.p, s);
+    launch_knn_load(Q, q_dtype, q_stride_cell, q_stride_col, n_q, d, Q64.p, qsums.p, s);
+    launch_knn_center(R64.p, n_r, nr_pad, d, dp, rsums.p, n_r, R32.p, cn.p, s);
+    launch_knn_center(Q64.p, n_q, nq_pad, d, dp, rsums.p, n_r, Q32.p, nullptr, s);
+    KnnSearchArgs ka{};
+    ka.Xq = Q32.p; ka.Xr = R32.p; ka.cn = cn.p; ka.nq = n_q; ka.nq_pad = nq_pad; ka.dp = dp; ka.cap = cap;
+    ka.ntiles = ntiles; ka.tiles_per_slice = tps; ka.lists = lists.p; ka.counts = counts.p;
+    if (launch_knn_search(ka, s)) return fail(HMX_ERR_ARG, "unsupported d");
+    KnnFinishArgs fa{};
+    fa.Q = Q64.p; fa.R = R64.p; fa.nq = n_q; fa.nq_pad = nq_pad; fa.nr = n_r; fa.d = d; fa.k = k; fa.slices = S; fa.cap = cap;
+    fa.lists = lists.p; fa.counts = counts.p; fa.labels = labels.p; fa.n_labels = n_labels;
+    fa.pred = pred_out; fa.prob = prob_out; fa.dist = knn_dist_out; fa.idx = knn_idx_out;
+    launch_knn_finish(fa, s);
+    HIP_TRY(hipStreamSynchronize(s));                                         // (the temporaries are released on return)
+    HIP_TRY(hipGetLastError());
+    return HMX_OK;
 }
 
 int hmx_kmeans_seed(hmx_engine* e, const float* points, int64_t n_points, uint64_t seed, float* centers_out, int32_t* chosen_out) {

@@ -276,6 +276,39 @@ int launch_lisi_prepare_device(const void* src, int dtype, int64_t s_cell, int64
 int launch_lisi_knn(const LisiKnnArgs& a, hipStream_t s);
 int lisi_list_cap(int nn);          // 0: more neighbours than the largest list ranks
 void launch_lisi_finish(const LisiFinishArgs& a, hipStream_t s);
+// cross-set kNN (hmx_lisi.hip, hmx_knn_predict): the query set against the reference set, the reference cut into slices
+struct KnnSearchArgs {
+    const float* Xq;                // nq_pad x dp query rows centred by the reference's means (zero padded)
+    const float* Xr;                // nr_pad x dp centred reference rows
+    const float* cn;                // nr_pad squared norms of Xr's rows, +inf for padding rows
+    int64_t nq, nq_pad;             // nq_pad: a multiple of 256
+    int dp, cap;                    // cap as LisiKnnArgs.cap
+    int ntiles, tiles_per_slice;    // 16-row reference tiles; slice s streams s * tiles_per_slice .. (the last one fewer)
+    unsigned long long* lists;      // slices x nq_pad x cap
+    int* counts;                    // slices x nq
+};
+struct KnnFinishArgs {
+    const double* Q;                // nq x d float64 queries
+    const double* R;                // nr x d float64 reference rows
+    int64_t nq, nq_pad, nr;
+    int d, k, slices, cap;
+    const unsigned long long* lists;
+    const int* counts;
+    const int* labels;              // n_labels x nr category codes
+    int n_labels;
+    int* pred;                      // nq x n_labels (n_labels > 0)
+    double* prob;
+    double* dist;                   // nq x k or null
+    int* idx;
+};
+// typed read of a caller's device matrix into X (n x d float64) with its column sums; 1 for an unknown dtype
+int launch_knn_load(const void* src, int dtype, int64_t s_cell, int64_t s_col, int64_t n, int d, double* X, double* sums, hipStream_t s);
+void launch_knn_center(const double* X, int64_t n, int64_t npad, int d, int dp, const double* ref_sums, int64_t n_ref, float* X32,
+                       float* cn, hipStream_t s);
+int knn_queries_per_workgroup(int dp);
+int knn_search_workgroups_per_cu(int dp, int cap);   // resident k_knn_search workgroups per CU (the occupancy API)
+int launch_knn_search(const KnnSearchArgs& a, hipStream_t s);
+void launch_knn_finish(const KnnFinishArgs& a, hipStream_t s);
 
 // k-means++ seeding on the device (k_seed_*): n points of d floats, row-major X and its transpose Xt
 struct SeedArgs {

@@ -174,3 +174,11 @@ class HarmonyQuery(_EngineArrays):
     def result(self):
         """The mapped query as a NumPy array (N x d)."""
         return self.Z_corr
+
+    def knn_predict(self, reference_Z_corr, ref_meta, label_colnames, k=5, return_neighbors=False):
+        """The reference's labels transferred to the mapped query: ``knn_predict(self.to_tensor("Z_corr"),
+        reference_Z_corr, ...)`` (see there).  ``reference_Z_corr``: the reference's corrected embedding, cells x PCs
+        (``Harmony.to_tensor("Z_corr")`` keeps it on the device), with ``ref_meta`` one row per reference cell."""
+        from .knn import knn_predict
+        return knn_predict(self.to_tensor("Z_corr"), reference_Z_corr, ref_meta, label_colnames, k=k,
+                           return_neighbors=return_neighbors)
