@@ -1,4 +1,4 @@
-"""ctypes binding of libhmx.so (include/hmx.h, include/hmx_device_io.h, include/hmx_map.h, include/hmx_knn.h).  Thin: argument marshalling and error text only.
+"""ctypes binding of libhmx.so (include/hmx.h, include/hmx_device_io.h, include/hmx_map.h, include/hmx_knn.h, include/hmx_score.h).  Thin: argument marshalling and error text only.
 
 The library is the product's compute path; there is no fallback.  Importing this module
 without a built ``libhmx.so`` raises, and every entry point raises ``HmxError`` with the
@@ -35,6 +35,8 @@ DEVICE_IO_EXPORTS = ["hmx_upload_device", "hmx_copy_out_device", "hmx_compute_li
 MAP_EXPORTS = ["hmx_reference_summary", "hmx_map_query"]
 # include/hmx_knn.h: cross-set kNN and label vote (same ABI version; its own header)
 KNN_EXPORTS = ["hmx_knn_predict", "hmx_knn_slices"]
+# include/hmx_score.h: cluster moments and the per-cell mapping score (same ABI version; its own header)
+SCORE_EXPORTS = ["hmx_cluster_moments", "hmx_mapping_score"]
 HMX_PEER_HANDLE_BYTES = 64
 HMX_ABI_VERSION = 8
 HMX_UNIQUE_ID_BYTES = 128
@@ -117,7 +119,9 @@ def load():
     lib.hmx_knn_predict.argtypes = [i32, vp, C.c_int, i64, i64, i64, vp, C.c_int, i64, i64, i64, i32, i32, i32, vp, vp, i32,
                                     vp, vp, vp, vp]
     lib.hmx_knn_slices.argtypes = [i32, i64, i64, i32, i32]
-    for name in EXPORTS + DEVICE_IO_EXPORTS + MAP_EXPORTS + KNN_EXPORTS:
+    lib.hmx_cluster_moments.argtypes = [vp, C.c_int, vp, i32, vp, vp, vp, vp]
+    lib.hmx_mapping_score.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    for name in EXPORTS + DEVICE_IO_EXPORTS + MAP_EXPORTS + KNN_EXPORTS + SCORE_EXPORTS:
         if name not in ("hmx_last_error", "hmx_destroy", "hmx_build_id"):
             getattr(lib, name).restype = C.c_int
     lib.hmx_build_id.restype = C.c_char_p
@@ -327,6 +331,34 @@ class Engine:
         mass = _c(cluster_mass, np.float64)
         assert sums.shape == (self.K, self.d) and mass.shape == (self.K,)
         _check(self._lib.hmx_map_query(self._h, _ptr(sums), _ptr(mass)))
+
+    def cluster_moments(self, which_Z, codes=None, n_groups=None):
+        """(mass G, mass_sq G, mean G x d, cov G x d x d), float64: the weighted moments of the cells in ``which_Z``
+        (HMX_Z_ORIG / HMX_Z_CORR) under the soft assignment R, or under ``codes`` (N group codes in the caller's cell
+        order, ``n_groups`` groups) (hmx_cluster_moments).  The state is not touched."""
+        G = self.K if codes is None else int(n_groups)
+        codes = None if codes is None else _c(codes, np.int32)
+        assert codes is None or codes.shape == (self.N,)
+        mass, mass_sq = np.empty(G, np.float64), np.empty(G, np.float64)
+        mean, cov = np.empty((G, self.d), np.float64), np.empty((G, self.d, self.d), np.float64)
+        _check(self._lib.hmx_cluster_moments(self._h, int(which_Z), _ptr(codes), G, _ptr(mass), _ptr(mass_sq), _ptr(mean),
+                                             _ptr(cov)))
+        return mass, mass_sq, mean, cov
+
+    def mapping_score(self, which_Z, whitening, offsets, out_ptr=None, stream=0):
+        """score[j] = sum_k R[k,j] |T_k x_j - t_k| for every cell, caller's order (hmx_mapping_score): ``whitening`` K x d x d
+        lower-triangular T_k, ``offsets`` K x d.  Returns N float64 on the host, or with ``out_ptr`` (device address of N
+        contiguous float64, ordered on ``stream``) writes there and returns None."""
+        T = _c(whitening, np.float64)
+        t = _c(offsets, np.float64)
+        assert T.shape == (self.K, self.d, self.d) and t.shape == (self.K, self.d)
+        if out_ptr is None:
+            out = np.empty(self.N, np.float64)
+            _check(self._lib.hmx_mapping_score(self._h, int(which_Z), _ptr(T), _ptr(t), _ptr(out), None, None))
+            return out
+        _check(self._lib.hmx_mapping_score(self._h, int(which_Z), _ptr(T), _ptr(t), None, C.c_void_p(int(out_ptr)),
+                                           C.c_void_p(int(stream) or None)))
+        return None
 
     _SHAPES = {
         HMX_Z_ORIG: ("N", "d", np.float32), HMX_Z_COS: ("N", "d", np.float32), HMX_Z_CORR: ("N", "d", np.float32),

@@ -17,7 +17,9 @@
 #include "hmx_device_io.h"
 #include "hmx_knn.h"
 #include "hmx_map.h"
+#include "hmx_score.h"
 #include "hmx_internal.h"
+#include "hmx_score_kernels.h"
 #ifdef RTZ_PROF
 void rtz_prof_dump();
 #endif
@@ -2451,6 +2453,174 @@ int hmx_kernel_times(hmx_engine* e, double* ms_out, int n, const char** names_ou
     for (int i = 0; i < F_COUNT && 2 * i + 1 < n; ++i) { ms_out[2 * i] = e->fam_ms[i]; ms_out[2 * i + 1] = (double)e->fam_n[i]; }
     if (names_out) *names_out = kFamilyNames;
     return F_COUNT;
+}
+
+// ---- mapping confidence (include/hmx_score.h) -----------------------------------------------------
+
+// what both entry points ask of the engine; *Z = the embedding which_Z names
+static int score_engine_checks(hmx_engine* e, int which_Z, const char* who, const float** Z) {
+    if (!e->uploaded) return fail(HMX_ERR_STATE, "%s: hmx_upload must come first", who);
+    if (!e->clustered) return fail(HMX_ERR_STATE, "%s: no soft assignment yet", who);
+    if (sharded(e) || e->n_ranks > 1 || e->Ng != e->N)
+        return fail(HMX_ERR_STATE, "%s: this engine holds one shard of a sharded job; mapping confidence needs all cells on one engine", who);
+    if (which_Z != HMX_Z_ORIG && which_Z != HMX_Z_CORR) return fail(HMX_ERR_ARG, "%s: which_Z must be HMX_Z_ORIG or HMX_Z_CORR (%d)", who, which_Z);
+    *Z = which_Z == HMX_Z_ORIG ? e->Zorig.p : e->Zcorr.p;
+    return 0;
+}
+
+// chunks of cells for a pass whose per-chunk slab holds `per_chunk` bytes: at least 1024 cells each, the slabs within
+// `budget` bytes (one chunk always), at most `cap` chunks; *chunk = cells per chunk, a multiple of 8
+static int score_chunks(int64_t N, size_t per_chunk, size_t budget, int cap, int64_t* chunk) {
+    int64_t c = std::min<int64_t>({(N + 1023) / 1024, (int64_t)(budget / std::max<size_t>(per_chunk, 1)), (int64_t)cap});
+    c = std::max<int64_t>(c, 1);
+    *chunk = (((N + c - 1) / c) + 7) & ~(int64_t)7;
+    return (int)((N + *chunk - 1) / *chunk);
+}
+
+int hmx_cluster_moments(hmx_engine* e, int which_Z, const int32_t* codes, int32_t n_groups, double* mass, double* mass_sq,
+                        double* mean, double* cov) {
+    if (!e || !mass || !mass_sq || !mean || !cov) return fail(HMX_ERR_ARG, "null argument");
+    const float* Z;
+    int rc;
+    if ((rc = score_engine_checks(e, which_Z, "hmx_cluster_moments", &Z))) return rc;
+    const int G = n_groups, d = e->d, dt = (d + 15) / 16;
+    if (!codes && G != e->K) return fail(HMX_ERR_ARG, "hmx_cluster_moments: without codes n_groups must be n_clusters (%d != %d)", G, e->K);
+    if (codes) {
+        if (G < 1 || G > 4096) return fail(HMX_ERR_ARG, "hmx_cluster_moments: n_groups must lie in [1, 4096] (%d)", G);
+        if (!e->map_perm) return fail(HMX_ERR_STATE, "hmx_cluster_moments: the upload's source_row is not a permutation of the cells");
+        for (int64_t i = 0; i < e->N; ++i)
+            if (codes[i] < 0 || codes[i] >= G) return fail(HMX_ERR_ARG, "hmx_cluster_moments: codes[%lld] = %d out of range", (long long)i, codes[i]);
+    }
+    if ((rc = use_device(e))) return rc;
+    MomArgs a{};
+    a.R = codes ? nullptr : e->R.p; a.map = e->cell_map.p; a.Z = Z; a.N = e->N;
+    a.Kp = e->Kp; a.dp = e->dp; a.d = d; a.dt = dt; a.G = G; a.G16 = (G + 15) & ~15;
+    a.ld1 = 16 * dt + 2; a.nt = dt * (dt + 1) / 2;
+    const size_t n_sums = (size_t)a.G16 * a.ld1, n_tiles = (size_t)G * a.nt * 256;
+    // the folded tiles are held once on the device beside at least one chunk's slab and once on the host: keep them to 1 GiB
+    if (n_tiles * sizeof(double) > ((size_t)1 << 30))
+        return fail(HMX_ERR_ARG, "hmx_cluster_moments: %d groups x %d PCs need %.1f GiB of covariance tiles (limit 1 GiB: n_groups * dt * (dt + 1) / 2 <= 524288, dt = ceil(n_pcs / 16)); score fewer groups per call",
+                    G, d, (double)(n_tiles * sizeof(double)) / ((size_t)1 << 30));
+    int64_t chunk1, chunk2;
+    const int C1 = score_chunks(e->N, n_sums * sizeof(double), (size_t)64 << 20, 2048, &chunk1);
+    const int C2 = score_chunks(e->N, n_tiles * sizeof(double), (size_t)256 << 20, 4096, &chunk2);
+    DevBuf<int> d_codes;
+    DevBuf<double> slab1, sums, meanb, slab2, tiles;
+    auto release = [&]() { d_codes.release(); slab1.release(); sums.release(); meanb.release(); slab2.release(); tiles.release(); };
+    std::vector<double> h_sums(n_sums), h_tiles(n_tiles);
+    auto run = [&]() -> int {
+        int r;
+        if ((r = slab1.reserve(n_sums * C1)) || (r = sums.reserve(n_sums)) || (r = meanb.reserve((size_t)a.G16 * 16 * dt)) ||
+            (r = slab2.reserve(n_tiles * C2)) || (r = tiles.reserve(n_tiles)))
+            return r;
+        if (codes) {
+            if ((r = d_codes.reserve(e->N))) return r;
+            HIP_TRY(hipMemcpyAsync(d_codes.p, codes, (size_t)e->N * sizeof(int), hipMemcpyHostToDevice, e->stream));
+        }
+        a.codes = d_codes.p; a.slab1 = slab1.p; a.sums = sums.p; a.mean = meanb.p; a.slab2 = slab2.p; a.tiles = tiles.p;
+        HIP_TRY(hipMemsetAsync(slab1.p, 0, n_sums * C1 * sizeof(double), e->stream));   // the mass columns of the column blocks behind the first
+        a.chunk = chunk1; a.nchunks = C1;
+        launch_mom_sums(a, e->stream);
+        a.chunk = chunk2; a.nchunks = C2;
+        launch_mom_cov(a, e->stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h_sums.data(), sums.p, n_sums * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipMemcpyAsync(h_tiles.data(), tiles.p, n_tiles * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        return 0;
+    };
+    rc = run();
+    if (rc) (void)hipStreamSynchronize(e->stream);
+    release();
+    if (rc) return rc;
+    const double nan = std::nan("");
+    for (int g = 0; g < G; ++g) {
+        const double m = h_sums[(size_t)g * a.ld1 + 16 * dt], m2 = h_sums[(size_t)g * a.ld1 + 16 * dt + 1];
+        mass[g] = m;
+        mass_sq[g] = m2;
+        for (int j = 0; j < d; ++j) mean[(size_t)g * d + j] = m > 0.0 ? h_sums[(size_t)g * a.ld1 + j] / m : nan;
+        double* cg = cov + (size_t)g * d * d;
+        const double unbias = 1.0 - m2 / (m * m);
+        int t = 0;
+        for (int ti = 0; ti < dt; ++ti)
+            for (int tj = ti; tj < dt; ++tj, ++t) {
+                const double* tile = h_tiles.data() + ((size_t)g * a.nt + t) * 256;
+                for (int r = 0; r < 4; ++r)
+                    for (int l = 0; l < 64; ++l) {
+                        const int i = 16 * ti + (l >> 4) + 4 * r, j = 16 * tj + (l & 15);
+                        if (i >= d || j >= d || i > j) continue;          // the upper triangle, mirrored: exactly symmetric
+                        const double v = m > 0.0 ? tile[r * 64 + l] / m / unbias : nan;
+                        cg[(size_t)i * d + j] = v;
+                        cg[(size_t)j * d + i] = v;
+                    }
+            }
+    }
+    return HMX_OK;
+}
+
+int hmx_mapping_score(hmx_engine* e, int which_Z, const double* whitening, const double* offsets, double* score_host,
+                      void* score_device, void* stream) {
+    if (!e || !whitening || !offsets) return fail(HMX_ERR_ARG, "null argument");
+    if (!score_host == !score_device) return fail(HMX_ERR_ARG, "hmx_mapping_score: exactly one of score_host and score_device");
+    const float* Z;
+    int rc;
+    if ((rc = score_engine_checks(e, which_Z, "hmx_mapping_score", &Z))) return rc;
+    if (!e->map_perm) return fail(HMX_ERR_STATE, "hmx_mapping_score: the upload's source_row is not a permutation of the cells");
+    const int K = e->K, d = e->d, dt = (d + 15) / 16, dp16 = 16 * dt;
+    const size_t fragD = mscore_frag_doubles(dt);
+    std::vector<double> P((size_t)K * fragD, 0.0), off((size_t)K * dp16, 0.0);
+    for (int k = 0; k < K; ++k) {
+        const double* T = whitening + (size_t)k * d * d;
+        for (int i = 0; i < d; ++i) {
+            const double t = offsets[(size_t)k * d + i];
+            if (!std::isfinite(t)) return fail(HMX_ERR_ARG, "hmx_mapping_score: offsets[%d][%d] is not finite", k, i);
+            off[(size_t)k * dp16 + i] = t;
+            for (int j = 0; j <= i; ++j)
+                if (!std::isfinite(T[(size_t)i * d + j])) return fail(HMX_ERR_ARG, "hmx_mapping_score: whitening[%d][%d][%d] is not finite", k, i, j);
+        }
+        for (int ti = 0; ti < dt; ++ti) {
+            double* f = P.data() + (size_t)k * fragD + mscore_frag_offset(ti);
+            for (int kc = 0; kc < 4 * (ti + 1); ++kc)
+                for (int l = 0; l < 64; ++l) {
+                    const int row = 16 * ti + (l & 15), col = 4 * kc + (l >> 4);
+                    if (row < d && col <= row) f[(size_t)kc * 64 + l] = T[(size_t)row * d + col];
+                }
+        }
+    }
+    if ((rc = use_device(e))) return rc;
+    DevBuf<double> dT, dOff, dOut;
+    auto release = [&]() { dT.release(); dOff.release(); dOut.release(); };
+    hipStream_t caller = static_cast<hipStream_t>(stream);
+    auto run = [&]() -> int {
+        int r;
+        if ((r = dT.reserve(P.size())) || (r = dOff.reserve(off.size()))) return r;
+        if (score_host && (r = dOut.reserve(e->N))) return r;
+        if (score_device) {
+            if ((r = io_events(e))) return r;
+            HIP_TRY(hipEventRecord(e->io_ev[0], caller));           // the destination may still be in use on the caller's stream
+            HIP_TRY(hipStreamWaitEvent(e->stream, e->io_ev[0], 0));
+        }
+        HIP_TRY(hipMemcpyAsync(dT.p, P.data(), P.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipMemcpyAsync(dOff.p, off.data(), off.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
+        MScoreArgs a{};
+        a.R = e->R.p; a.Z = Z; a.map = e->cell_map.p; a.T = dT.p; a.off = dOff.p;
+        a.out = score_host ? dOut.p : static_cast<double*>(score_device);
+        a.N = e->N; a.K = K; a.Kp = e->Kp; a.dp = e->dp; a.d = d; a.dt = dt;
+        launch_mscore(a, e->stream);
+        HIP_TRY(hipGetLastError());
+        if (score_host) {
+            HIP_TRY(hipMemcpyAsync(score_host, dOut.p, (size_t)e->N * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+        } else {
+            HIP_TRY(hipEventRecord(e->io_ev[1], e->stream));        // the caller's later work sees the scores
+            HIP_TRY(hipStreamWaitEvent(caller, e->io_ev[1], 0));
+        }
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        return 0;
+    };
+    rc = run();
+    if (rc) (void)hipStreamSynchronize(e->stream);
+    release();
+    return rc ? rc : HMX_OK;
 }
 
 }  // extern "C"

@@ -697,6 +697,15 @@ class Harmony(_EngineArrays):
         sums, mass = self._engine.reference_summary()
         return HarmonyReference(sums, mass, self._sigma, self.N_global)
 
+    def cluster_moments(self, space="orig"):
+        """``ClusterMoments`` of the current state: per cluster the mass, the weighted mean and the unbiased weighted
+        covariance of the cells under the soft assignment R, in ``space`` = "orig" (the PCs before correction, what
+        ``HarmonyQuery.mapping_score`` measures a query in by default) or "corr" (Z_corr).  Float64 sums on the device
+        (hmx_cluster_moments); the state itself is not changed.  Not available on one shard of a sharded job."""
+        from .confidence import SPACES, ClusterMoments, _check_space
+        _check_space(space)
+        return ClusterMoments(*self._engine.cluster_moments(SPACES[space]), space, self.N)
+
     # ------------------------------------------------------------------
     # harmony.py:366-392
     # ------------------------------------------------------------------

@@ -182,3 +182,35 @@ class HarmonyQuery(_EngineArrays):
         from .knn import knn_predict
         return knn_predict(self.to_tensor("Z_corr"), reference_Z_corr, ref_meta, label_colnames, k=k,
                            return_neighbors=return_neighbors)
+
+    def cluster_moments(self, space="orig", groups=None):
+        """``ClusterMoments`` of the query's cells in ``space`` ("orig": the query's PCs as given, "corr": mapped): under
+        its soft assignment to the reference's clusters, or, with ``groups`` (one label per cell, anything
+        ``pd.Categorical`` takes), per group in the order of the categories.  A group without cells has NaN moments."""
+        from .confidence import query_moments
+        return query_moments(self, space, groups)
+
+    def mapping_score(self, moments, ridge=0.0, as_tensor=False):
+        """Per-cell mapping confidence (Symphony's per-cell mapping metric): ``score[j] = sum_k R[j,k] D[k,j]`` with
+        ``D[k,j]`` the Mahalanobis distance of query cell j from reference cluster k, ``sqrt((x_j - mean_k)^T (cov_k +
+        ridge (tr cov_k / d) I)^-1 (x_j - mean_k))``.  Low: the cell lies inside the reference clusters it was assigned to
+        (for Gaussian clusters D^2 averages d); high: the reference has nothing like it.
+
+        ``moments``: the reference's ``ClusterMoments`` (``Harmony.cluster_moments``, ``ClusterMoments.from_arrays``,
+        ``ClusterMoments.load``) or the finished ``Harmony`` itself (its ``cluster_moments("orig")``); the query is
+        measured in the space the moments were taken in.  Returns N float64 in the caller's cell order: NumPy, or with
+        ``as_tensor`` a tensor on the engine's device, ordered on the current stream, with the same bits.  ValueError
+        for a K or d mismatch, non-finite moments, a negative ridge, or clusters whose covariance is not positive
+        definite (``ridge > 0`` regularises them)."""
+        from .confidence import mapping_score
+        return mapping_score(self, moments, ridge, as_tensor)
+
+    def cluster_mapping_score(self, moments, groups, ridge=0.0, min_cells_per_dim=2):
+        """Per-cluster mapping confidence (Symphony's per-cluster mapping metric) for the query groups ``groups`` (one
+        label per cell: the query's own clustering, predicted labels): the Mahalanobis distance of every reference
+        cluster mean from the group's mean in the group's own covariance (+ ridge (tr / d) I), averaged with the
+        group's mean soft assignment.  Returns a DataFrame indexed by the categories of ``pd.Categorical(groups)`` with
+        ``n_cells`` and ``score``; NaN for a group of fewer than ``min_cells_per_dim * d`` cells or with a covariance
+        that is not positive definite."""
+        from .confidence import cluster_mapping_score
+        return cluster_mapping_score(self, moments, groups, ridge, min_cells_per_dim)
