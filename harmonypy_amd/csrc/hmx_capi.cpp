@@ -177,6 +177,7 @@ struct hmx_engine {
     int rtz_kernel = 3;                  // HMX_RTZ=2: the list-order kernel k_rtz2 everywhere (A/B timing, fall-back)
     bool static_contig = false;          // every static tile holds consecutive cells (what harmonypy_amd builds)
     int ntasks3 = 0;
+    int task3_tiles_max = 0;             // static tiles of the largest of these tasks (hmx_counters out[13])
     DevBuf<int> t3_t0, t3_t1, t3_c0, t3_cend, t3_grp, t3_stride, s_tile_start;
     DevBuf<unsigned char> tile_blk[2], tile_blk_zero;
     DevBuf<unsigned> Yf;                 // wide shapes: the round's Y as bf16 fragments for k_assign_wide3 (launch_y_planes)
@@ -702,6 +703,7 @@ int upload_impl(hmx_engine* e, const ZSource& z, const int32_t* static_cells, in
             if (tstart[g + 1] > tstart[g] && static_cells[(size_t)tstart[g] * HMX_TILE] != gs2[g]) contig = false;
         e->static_contig = contig;
         e->ntasks3 = 0;
+        e->task3_tiles_max = 0;
         if (contig) {
             std::vector<int> a0, a1, ac0, acend, ag, ast;
             // k_rtz3 keeps two workgroups per CU resident, k_rtz3c (sixteen tile buffers) one: as many tasks as fit at once,
@@ -732,6 +734,9 @@ int upload_impl(hmx_engine* e, const ZSource& z, const int32_t* static_cells, in
                 const int m = (te - ts + CH3 - 1) / CH3, per = (te - ts + m - 1) / m;
                 if (interleave) {
                     const int mm = std::min(m, (te - ts + quad - 1) / quad);       // no task without a tile
+                    // (the group's first task holds the most tiles: the quads 0, mm, 2 mm, ... of the group's nq, the last one maybe short)
+                    const int nq = (te - ts + quad - 1) / quad, first = (nq + mm - 1) / mm;
+                    e->task3_tiles_max = std::max(e->task3_tiles_max, quad * first - ((nq - 1) % mm == 0 ? quad * nq - (te - ts) : 0));
                     for (int j = 0; j < mm; ++j) {
                         a0.push_back(ts + quad * j); a1.push_back(te); ag.push_back(g); ast.push_back(quad * mm);
                         ac0.push_back(gs2[g] + quad * j * HMX_TILE); acend.push_back(gs2[g + 1]);
@@ -739,6 +744,7 @@ int upload_impl(hmx_engine* e, const ZSource& z, const int32_t* static_cells, in
                     continue;
                 }
                 for (int i = ts; i < te; i += per) {
+                    e->task3_tiles_max = std::max(e->task3_tiles_max, std::min(i + per, te) - i);
                     a0.push_back(i); a1.push_back(std::min(i + per, te)); ag.push_back(g); ast.push_back(quad);
                     ac0.push_back(gs2[g] + (i - ts) * HMX_TILE); acend.push_back(gs2[g + 1]);
                 }
@@ -1614,6 +1620,7 @@ static int round_body(hmx_engine* e, int flags, int n_tiles_upper, const std::ve
             if (multi) {
                 ra.peer_box = e->peer_dev.p; ra.my_box = e->box; ra.n_ranks = e->n_ranks; ra.rank = e->rank;
                 ra.epoch = e->round_epoch;
+                static_assert(HMX_MAX_BLOCKS < 256, "the peer flags of two launches are 256 apart: a launch's block count must stay below that");
                 e->round_epoch += 256;   // (> HMX_MAX_BLOCKS: the flag values of two launches never meet)
             }
 #ifdef HMX_ROUND_PROF
@@ -2417,7 +2424,8 @@ int hmx_counters(hmx_engine* e, int64_t out[HMX_N_COUNTERS]) {
     out[10] = e->box ? (e->box_fine ? 2 : 1) : 0;
     out[11] = e->n_rtz_zf;
     out[12] = e->n_sweeps_wide;
-    for (int i = 13; i < HMX_N_COUNTERS; ++i) out[i] = 0;
+    out[13] = e->task3_tiles_max;
+    for (int i = 14; i < HMX_N_COUNTERS; ++i) out[i] = 0;
     return HMX_OK;
 }
 

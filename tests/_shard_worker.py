@@ -3,9 +3,15 @@
 MASTER_ADDR / MASTER_PORT in the environment (gloo rendezvous on 127.0.0.1).
 
 modes
-  oracle   the cell-sharded CPU oracle (oracle/sharded_oracle.py) behind the product's own
-           sharded front end (harmonypy_amd.harmony._prepare_inputs + dist.Shard)     [CPU]
-  engine   harmonypy_amd.run_harmony(..., shard=Shard(transport=<opt>)) on the GPU     [GPU]
+  oracle     the cell-sharded CPU oracle (oracle/sharded_oracle.py) behind the product's own
+             sharded front end (harmonypy_amd.harmony._prepare_inputs + dist.Shard)     [CPU]
+  engine     harmonypy_amd.run_harmony(..., shard=Shard(transport=<opt>)) on the GPU     [GPU]
+  synthetic  a synthetic job from the options instead of a golden case (<case> is a label only):
+             N, d, B, K, data_seed, sort_by_batch -> synthetic_job(); cuts = the world + 1 cut points
+             of the ranks' slices; rounds = the forced schedule, e.g. [3, 2]; seed = the engine seed.
+             The initial centroids come from <outdir>/Y0.npy (written once by the parent).  Device
+             update order; per Harmony iteration cluster(_rounds=r), a snapshot of this rank's rows
+             of R and of O / E / Y, then moe_correct_ridge() and a snapshot of Z_corr             [GPU]
 Every rank writes <outdir>/rank<r>.npz with its slice of Z_corr and the objective history.
 """
 import json
@@ -18,15 +24,60 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+COUNTERS = ("sweep_fallbacks", "sweep_waits", "sweeps_bf16_pipe", "sweeps_group_affine", "rtz_bf16_pipe", "peer_box")
+
+
+def synthetic_job(opts):
+    """(Z cells x d, meta) of the synthetic job `opts` describes, in the job's cell order: bench.synthetic_dataset, and with
+    ``sort_by_batch`` its cells ordered by batch (stable), so that a contiguous slice holds only a few of the batch groups.
+    The parent of a sharded test hands the same arrays to the unsharded oracle."""
+    from bench import synthetic_dataset
+    Z, meta = synthetic_dataset(int(opts["N"]), int(opts["d"]), int(opts["B"]), int(opts["K"]), seed=int(opts.get("data_seed", 3)))
+    if opts.get("sort_by_batch"):
+        by_batch = np.argsort(meta["batch"].cat.codes.to_numpy(), kind="stable")
+        Z, meta = np.ascontiguousarray(Z[by_batch]), meta.iloc[by_batch].reset_index(drop=True)
+    return Z, meta
+
+
+def run_synthetic(opts, outdir, rank, world):
+    """This rank's slice of a synthetic job on the GPU, iteration by iteration; returns what the rank writes."""
+    os.environ["HMX_UPDATE_ORDER"] = "device"
+    from harmonypy_amd import Shard
+    from harmonypy_amd import harmony as H
+    Z, meta = synthetic_job(opts)
+    cuts = [int(c) for c in opts["cuts"]]
+    assert len(cuts) == world + 1 and cuts[0] == 0 and cuts[-1] == Z.shape[0] and all(a < b for a, b in zip(cuts, cuts[1:])), cuts
+    lo, hi = cuts[rank], cuts[rank + 1]
+    Y0 = np.load(os.path.join(outdir, "Y0.npy"))
+    shard = Shard(transport=opts.get("transport", "host"))
+    ho = H.run_harmony(Z[lo:hi], meta.iloc[lo:hi].reset_index(drop=True), ["batch"], nclust=int(opts["K"]), max_iter_harmony=0,
+                       random_state=int(opts["seed"]), verbose=False, shard=shard, _y0=Y0)
+    assert ho.update_order == "device" and (ho._offset, ho.N_global) == (lo, Z.shape[0])
+    out = dict(lo=lo, hi=hi, groups_held=np.unique(ho._gid_int).size, groups=ho._G)
+    for it, r in enumerate(opts["rounds"]):
+        ho.cluster(_rounds=int(r))
+        out.update({f"R_{it}": ho.R, f"O_{it}": ho.O, f"E_{it}": ho.E, f"Y_{it}": ho.Y})
+        ho.moe_correct_ridge()
+        out[f"Z_corr_{it}"] = ho.Z_corr
+    cnt = ho._engine.counters()
+    out.update(objective_kmeans=ho.objective_kmeans, objective_harmony=ho.objective_harmony, kmeans_rounds=ho.kmeans_rounds,
+               transport=str(ho.transport), **{k: cnt[k] for k in COUNTERS})
+    return out
+
 
 def main():
     mode, case, outdir = sys.argv[1:4]
     opts = json.loads(sys.argv[4]) if len(sys.argv) > 4 else {}
     import torch
     import torch.distributed as dist
-    from conftest import load_case
     dist.init_process_group("gloo")
     rank, world = dist.get_rank(), dist.get_world_size()
+    if mode == "synthetic":
+        np.savez(os.path.join(outdir, f"rank{rank}.npz"), **run_synthetic(opts, outdir, rank, world))
+        dist.barrier()
+        dist.destroy_process_group()
+        return
+    from conftest import load_case
 
     data, meta, vars_use, kw, g = load_case(case)
     kw.update(opts.get("kw", {}))

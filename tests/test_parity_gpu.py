@@ -535,6 +535,19 @@ def test_bench_path_parity_many_batches(ga, monkeypatch):
         assert cnt["sweeps_group_affine"] == 0 and cnt["sweeps_bf16_pipe"] == 0, cnt
 
 
+@pytest.mark.parametrize("ga", ["1", "0"])
+def test_bench_path_parity_config4_shape(ga, monkeypatch):
+    """BASELINE configs[3]'s shape (d=50, K=100, SIXTEEN batches) at 160k cells on one engine, on the group-affine and on the
+    classic tile map (HMX_ROUND_GA=0: the map a sharded engine uses): same checks as the C3 shape.  16 groups' tables fit next to
+    the bf16 planes on either map (21 is the most on the classic one), so every sweep is a persistent bf16-pipe launch."""
+    monkeypatch.setenv("HMX_ROUND_GA", ga)
+    rounds = (3, 3)
+    ho = _bench_path_case(160_000, 50, 16, 100, monkeypatch, ridge_dtype=np.float64, rounds=rounds)
+    cnt = ho._engine.counters()
+    assert cnt["sweep_waits"] > 0 and cnt["sweep_fallbacks"] == 0, cnt
+    assert cnt["sweeps_group_affine"] == (sum(rounds) if ga == "1" else 0) and cnt["sweeps_bf16_pipe"] == sum(rounds), cnt
+
+
 def _ab_engines(N, d, B, K, monkeypatch, switch, value, **kw):
     """Two engines in ONE process on the same uploaded state, Y0 and seed (device update order): the default instances and
     the ones an engine created under `switch`=`value` selects (the switches are read by hmx_create, per engine)."""
@@ -866,7 +879,7 @@ WIDE_REPEAT_SHAPES = [(1500, 70, 20, 2, 0.1), (1500, 70, 20, 2, 0.05), (1500, 70
 
 @pytest.mark.parametrize("N,d,K,B,bs", WIDE_REPEAT_SHAPES)
 def test_wide_paths_are_repeatable(N, d, K, B, bs):
-    """The wide assignment path (K > 112 or d > 64: one k_assign_wide2 launch per update block) run 50 times on the same
+    """The wide assignment path (K > 112 or d > 64: k_assign_wide / k_assign_wide3 per update block, or one k_sweep_wide3 launch per sweep) run 50 times on the same
     input: EVERY repeat within 1e-4 of the oracle (Z_corr) with the oracle's objectives, and all repeats mutually equal --
     same round counts, R within 2e-6 (the only run-to-run freedom is the order of fp64 atomic additions of block sums)."""
     from oracle import oracle_run_harmony
@@ -1132,6 +1145,92 @@ def test_config3_full_size_properties():
     ho2 = _hm().run_harmony(Z, meta, ["batch"], nclust=K, verbose=False, random_state=0, max_iter_harmony=3)
     assert ho2.kmeans_rounds == ho.kmeans_rounds
     np.testing.assert_allclose(ho2.Z_corr[::1009], ho.Z_corr[::1009], rtol=1e-3, atol=1e-4)
+
+
+def _deep_rtz_y_error(Z, meta, K, monkeypatch, cap):
+    """A fresh engine over all cells (HMX_RTZ3_TASK_CAP=`cap`, None: the default), two Harmony iterations, then ONE more round:
+    its centroids Y against the column-normalised Z_cos^T R (harmony.py:443-444) of the state the round started from, evaluated in
+    torch float64 on the device.  Returns (engine, R and Z_cos before the round as device tensors, max |dY|, largest task in tiles)."""
+    import torch
+    if cap is None:
+        monkeypatch.delenv("HMX_RTZ3_TASK_CAP", raising=False)
+    else:
+        monkeypatch.setenv("HMX_RTZ3_TASK_CAP", str(cap))
+    ho = _hm().run_harmony(Z, meta, ["batch"], nclust=K, verbose=False, random_state=0, max_iter_harmony=2)
+    cnt = ho._engine.counters()
+    assert ho.update_order == "device" and cnt["rtz_bf16_pipe"] > 0 and cnt["sweep_fallbacks"] == 0, cnt
+    R, Zc = ho.to_tensor("R"), ho.to_tensor("Z_cos")
+    ho.cluster(_rounds=1)
+    num = torch.zeros((ho.d, K), dtype=torch.float64, device=R.device)
+    step = 1 << 20
+    for lo in range(0, ho.N, step):
+        num += Zc[lo:lo + step].double().T @ R[lo:lo + step].double()
+    want = (num / num.norm(dim=0, keepdim=True)).cpu().numpy()
+    return ho, R, Zc, float(np.abs(ho.Y.astype(np.float64) - want).max()), cnt["rtz_task_tiles_max"]
+
+
+def test_config3_all_cells_on_one_gpu(monkeypatch):
+    """BASELINE configs[3] with ALL its cells on one engine (10 M x 50 PCs, 16 batches, K = 100; the engine's large-job defaults,
+    two Harmony iterations): the only size at which the streaming R^T.Z pass cuts tasks of more than 2 048 tiles (hmx_counters
+    out[13], asserted first) -- a workgroup's fp32 accumulators then sum 2 600 tiles = 42 k cells before the finish kernel folds
+    the tasks in fp64.
+      Size-independent properties, as test_config3_full_size_properties (same tolerances), computed on the device in float64 through
+    Harmony.to_tensor: rows of R are distributions, sum_k O[k,b] = N_b, O's row sums = R's column sums, E = T Pr_b, Z_cos rows and
+    Y columns are unit vectors, Z_orig - Z_corr = R W_g on a sample.
+      The deep accumulation: Y of one more round against the column-normalised Z_cos^T R in torch float64 on the device
+    (harmony.py:443-444 restated), bar: the project's Y tolerance, atol 5e-6 on components of unit vectors -- with the default
+    tasks and, in a fresh engine, with HMX_RTZ3_TASK_CAP=2048.
+    Measured on an MI355X: NOT YET MEASURED (default tasks) / NOT YET MEASURED (cap 2 048)."""
+    import os, sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import torch
+    from bench import synthetic_dataset
+    from harmonypy_amd import _capi
+    N, d, B, K = 10_000_000, 50, 16, 100
+    Z, meta = synthetic_dataset(N, d, B, K, seed=0)
+    ho, R, Zc, dy, tiles = _deep_rtz_y_error(Z, meta, K, monkeypatch, None)
+    assert tiles > 2048, f"the R^T.Z tasks hold at most {tiles} tiles: the deep arrangement did not run"
+    assert (ho.N, ho.d, ho.K, ho.B) == (N, d, K, B) and len(ho.kmeans_rounds) == 3 and ho.kmeans_rounds[-1] == 1
+    assert np.isfinite(np.asarray(ho.objective_kmeans)).all() and ho.objective_harmony[-1] < ho.objective_harmony[0]
+    # properties of the state before the extra round (R, Z_cos) and of the tables after it
+    rows = torch.zeros(N, dtype=torch.float64, device=R.device)
+    step = 1 << 20
+    for lo in range(0, N, step):
+        rows[lo:lo + step] = R[lo:lo + step].double().sum(dim=1)
+    assert float((rows - 1).abs().max()) <= 5e-6 and float(R.min()) >= 0.0
+    zn = torch.cat([Zc[lo:lo + step].double().norm(dim=1) for lo in range(0, N, step)])
+    assert float((zn - 1).abs().max()) <= 3e-6
+    del rows, zn, R, Zc
+    R = ho.to_tensor("R")                                                    # ... after the extra round
+    Rsum = torch.zeros(K, dtype=torch.float64, device=R.device)
+    for lo in range(0, N, step):
+        Rsum += R[lo:lo + step].double().sum(dim=0)
+    Rsum = Rsum.cpu().numpy()
+    counts = np.bincount(meta["batch"].cat.codes, minlength=B)
+    O, E = ho.O, ho.E
+    np.testing.assert_allclose(O.sum(axis=0), counts, rtol=2e-5)
+    np.testing.assert_allclose(O.sum(axis=1), Rsum, rtol=2e-5)              # O is carried incrementally over all rounds
+    np.testing.assert_allclose(E, np.outer(Rsum, counts / N), rtol=2e-5)
+    np.testing.assert_allclose(np.linalg.norm(ho.Y, axis=0), 1.0, atol=3e-6)
+    print(f"configs[3], 10 M cells on one engine: rounds {ho.kmeans_rounds}, largest R^T.Z task {tiles} tiles, max|dY| vs float64 = {dy:.2e}")
+    # the ridge correction of a sample of cells from the device's own W (G x K x d), after a ridge step on the R just read
+    ho.moe_correct_ridge()
+    W = ho._engine.get(_capi.HMX_W)
+    idx = torch.arange(0, N, 49_999, device=R.device)
+    Rs = R[idx].double().cpu().numpy()
+    diff = (ho.to_tensor("Z_orig")[idx].double() - ho.to_tensor("Z_corr")[idx].double()).cpu().numpy()
+    grp = ho._gid_int[ho._rank[idx.cpu().numpy()]]
+    corr = np.einsum("nk,nkd->nd", Rs, W[grp].astype(np.float64))
+    np.testing.assert_allclose(diff, corr, rtol=0, atol=2e-5 * np.abs(Z).max())
+    del R, ho
+    import gc
+    gc.collect()
+    torch.cuda.empty_cache()
+    _, _, _, dy2, tiles2 = _deep_rtz_y_error(Z, meta, K, monkeypatch, 2048)
+    assert 0 < tiles2 <= 2048, tiles2
+    print(f"configs[3], 10 M cells, HMX_RTZ3_TASK_CAP=2048: largest task {tiles2} tiles, max|dY| vs float64 = {dy2:.2e}")
+    assert dy <= 5e-6, f"default tasks ({tiles} tiles): max|dY| = {dy:.2e}"
+    assert dy2 <= 5e-6, f"tasks capped at 2048 tiles: max|dY| = {dy2:.2e}"
 
 
 def test_abi_call_order_and_argument_errors():
