@@ -4,6 +4,7 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -47,15 +48,21 @@ int fail(int code, const char* fmt, ...) {
             return fail(HMX_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
     } while (0)
 
+#define HMX_RTZ2_WGS_PER_CU 4   /* k_rtz2 grid */
 #define HMX_DEFER_MAX 8   /* rounds of one cluster() call whose objective may be read back late (no decision hangs on them) */
 
 enum Family { F_ASSIGN_BLOCK = 0, F_ASSIGN_INIT, F_RTZ_ROUND, F_RTZ_REDUCE, F_BLOCK_TABLE, F_RIDGE_STATS, F_RIDGE_SOLVE, F_RIDGE_APPLY, F_COUNT };
 const char* kFamilyNames = "assign_block\0assign_init\0rtz_round\0rtz_reduce\0block_table\0ridge_stats\0ridge_solve\0ridge_apply\0";
 
+// A device allocation that frees itself; release() is for the places that free early on purpose.
 template <typename T>
 struct DevBuf {
     T* p = nullptr;
     size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
     int reserve(size_t count) {
         if (count <= n) return 0;
         if (p) (void)hipFree(p);
@@ -73,6 +80,13 @@ struct DevBuf {
     }
 };
 
+// Declared BEHIND a function's temporaries (so it runs before they die): on an early return work may still be queued
+// on the stream that reads or writes them.
+struct SyncOnExit {
+    hipStream_t s;
+    ~SyncOnExit() { (void)hipStreamSynchronize(s); }
+};
+
 }  // namespace
 
 struct hmx_engine {
@@ -80,8 +94,6 @@ struct hmx_engine {
     int64_t N = 0;
     int d = 0, dp = 0, K = 0, Kp = 0, K16 = 0, mt = 0, ntd = 0, ldy = 0, B = 0, G = 0, V = 0, nblk = 0;
     int max_wgs = 1024;
-    int ablate = 0;          // HMX_ABLATE: timing experiments only (results become wrong)
-    int tiles_per_wave = 1;  // k_assign_lds grid sizing (HMX_TILES_PER_WAVE)
     hipStream_t stream = nullptr;
     bool uploaded = false, clustered = false, timing = false;
     unsigned timing_mask = ~0u;  // kernel families that are bracketed with events while `timing` is on
@@ -117,10 +129,9 @@ struct hmx_engine {
     DevBuf<float> km_hn;         // device k-means: half squared norms of the centres
     DevBuf<double> km_sums;      // device k-means: K16 x (d+1) member sums and counts
     DevBuf<double> Sslots;       // k_round: (nblk + 1) x HMX_ROUND_SLOTS x (G + 1) x K16 (row G of a slot table: the cluster masses, group-affine map)
-    DevBuf<unsigned> sync_words; // k_round: {arrival counter, error flag}
+    unsigned* sync_words = nullptr;  // k_round: {arrival counter, error flag}, the tail of Sslots
     unsigned* sync_host = nullptr;  // pinned copy of sync_words
     int n_cus = 0;
-    int rtz_wgs_per_cu = 4;      // k_rtz2 grid (HMX_RTZ_WGS_PER_CU)
     int round_mode = 1;          // 1: persistent sweep kernel when the shape allows it, 0: one launch per block (HMX_ROUND_MODE=blocks)
     unsigned spin_limit = 1u << 24;  // polls a grid-wide wait may take (HMX_SPIN_LIMIT; tests shrink it to force the fall-back)
     long n_sweep_fallbacks = 0;  // rounds repeated through the per-block path after a wait timed out
@@ -174,6 +185,8 @@ struct hmx_engine {
     int n_s_tiles = 0, ntasks = 0;
     std::vector<int> h_task_grp;
     // the R^T.Z pass in storage order (k_rtz3): group-pure tasks over the static tiles, block ids in static tile order
+    int rtz3_task_cap = 0;               // HMX_RTZ3_TASK_CAP: tiles per task of the streaming pass (A/B runs and tests; 0: the cut's own cap)
+    int round_req = -1;                  // HMX_ROUND_REQ=0|1|2: row-request placement of the group-affine sweep (-1: chosen per shape)
     int rtz_kernel = 3;                  // HMX_RTZ=2: the list-order kernel k_rtz2 everywhere (A/B timing, fall-back)
     bool static_contig = false;          // every static tile holds consecutive cells (what harmonypy_amd builds)
     int ntasks3 = 0;
@@ -365,9 +378,38 @@ AssignArgs assign_args(hmx_engine* e) {
     a.Zcos = e->Zcos.p; a.Y = e->Y.p; a.sigma = e->sigma.p; a.rp = e->rp.p; a.lrp = e->lrp.p; a.R = e->R.p;
     a.obj = e->objacc;
     a.K = e->K; a.Kp = e->Kp; a.K16 = e->K16; a.mt = e->mt; a.dp = e->dp; a.ldy = e->ldy;
-    a.G = e->G; a.tiles_per_wave = e->tiles_per_wave; a.ablate = e->ablate;
+    a.G = e->G;
     a.bf16_pipe = e->allow_round_bf16 ? 1 : 0;
     return a;
+}
+
+bool env_flag(const char* name, bool unset) {
+    const char* v = getenv(name);
+    return v ? atoi(v) != 0 : unset;
+}
+long env_long(const char* name, long unset, long lo, long hi) {
+    const char* v = getenv(name);
+    return v ? std::max(lo, std::min(hi, atol(v))) : unset;
+}
+
+// The engine's A/B and test switches, read once per engine by hmx_create.
+void read_switches(hmx_engine* e) {
+    const char* mode = getenv("HMX_ROUND_MODE");
+    e->round_mode = (mode && std::string(mode) == "blocks") ? 0 : 1;
+    e->round_wgs_cap = (int)env_long("HMX_ROUND_WGS", 0, 0, INT_MAX);
+    e->round_req = (int)env_long("HMX_ROUND_REQ", -1, 0, 2);
+    e->rtz3_task_cap = (int)env_long("HMX_RTZ3_TASK_CAP", 0, 16, INT_MAX);
+    e->rtz_kernel = env_long("HMX_RTZ", 3, LONG_MIN, LONG_MAX) == 2 ? 2 : 3;
+    e->test_fail_sweep = env_long("HMX_TEST_FAIL_SWEEP", -1, LONG_MIN, LONG_MAX);
+    e->spin_limit = (unsigned)env_long("HMX_SPIN_LIMIT", 1L << 24, 0, LONG_MAX);   // 0: every wait of the persistent kernels gives up at once (tests)
+    e->prefetch_lists = env_flag("HMX_PREFETCH_LISTS", true);
+    e->allow_round_bf16 = !env_flag("HMX_ROUND_F32", false);
+    e->allow_round_ga = env_flag("HMX_ROUND_GA", true);
+    e->allow_rtz_bf16 = env_flag("HMX_RTZ3_BF16", true);
+    e->allow_zcf = env_flag("HMX_RTZW_ZF", true);
+    e->fuse_block_table = env_flag("HMX_FUSE_TABLE", true);
+    e->wide_sweep = env_flag("HMX_WIDE_SWEEP", true);
+    e->lists_beside_rtz = env_flag("HMX_LISTS_BESIDE_RTZ", true);
 }
 
 TableArgs table_args(hmx_engine* e) {
@@ -416,22 +458,7 @@ int hmx_create(const hmx_config* cfg, hmx_engine** out) {
     e->K16 = 16 * e->mt;
     e->ntd = (e->dp + 15) / 16;   // PC tiles cover the padded row (padding columns hold zeros)
     e->ldy = 16 * e->ntd;
-    if (const char* ab = getenv("HMX_ABLATE")) e->ablate = atoi(ab);
-    if (const char* tpw = getenv("HMX_TILES_PER_WAVE")) e->tiles_per_wave = std::max(1, atoi(tpw));
-    if (const char* rw = getenv("HMX_RTZ_WGS_PER_CU")) e->rtz_wgs_per_cu = std::max(1, std::min(8, atoi(rw)));
-    if (const char* rc_ = getenv("HMX_ROUND_WGS")) e->round_wgs_cap = std::max(0, atoi(rc_));
-    if (const char* pl = getenv("HMX_PREFETCH_LISTS")) e->prefetch_lists = atoi(pl) != 0;
-    if (const char* rm = getenv("HMX_ROUND_MODE")) e->round_mode = (std::string(rm) == "blocks") ? 0 : 1;
-    if (const char* rf = getenv("HMX_ROUND_F32")) e->allow_round_bf16 = atoi(rf) == 0;
-    if (const char* rg = getenv("HMX_ROUND_GA")) e->allow_round_ga = atoi(rg) != 0;
-    if (const char* rb = getenv("HMX_RTZ3_BF16")) e->allow_rtz_bf16 = atoi(rb) != 0;
-    if (const char* zf = getenv("HMX_RTZW_ZF")) e->allow_zcf = atoi(zf) != 0;
-    if (const char* ft = getenv("HMX_FUSE_TABLE")) e->fuse_block_table = atoi(ft) != 0;
-    if (const char* rk = getenv("HMX_RTZ")) e->rtz_kernel = atoi(rk) == 2 ? 2 : 3;
-    if (const char* fs = getenv("HMX_TEST_FAIL_SWEEP")) e->test_fail_sweep = atol(fs);
-    if (const char* ws = getenv("HMX_WIDE_SWEEP")) e->wide_sweep = atoi(ws) != 0;
-    if (const char* lb = getenv("HMX_LISTS_BESIDE_RTZ")) e->lists_beside_rtz = atoi(lb) != 0;
-    if (const char* sl = getenv("HMX_SPIN_LIMIT")) e->spin_limit = (unsigned)std::max(0L, atol(sl));   // 0: every wait of the persistent kernels gives up at once (tests)
+    read_switches(e);
     int rc = 0;
     do {
         if ((rc = use_device(e))) break;
@@ -465,8 +492,7 @@ int hmx_create(const hmx_config* cfg, hmx_engine** out) {
         }
         if ((rc = e->Sslots.reserve(GKs * (e->nblk + 1) * HMX_ROUND_SLOTS + 1 + 160 + 256)) || (rc = e->wait_stats.reserve(8))) break;   // + slack: the per-round fill is rounded up to 1 KB
         (void)hipMemsetAsync(e->wait_stats.p, 0, 8 * sizeof(unsigned long long), e->stream);
-        e->sync_words.p = reinterpret_cast<unsigned*>(e->Sslots.p + GKs * (e->nblk + 1) * HMX_ROUND_SLOTS);   // borrowed tail
-        e->sync_words.n = 2;
+        e->sync_words = reinterpret_cast<unsigned*>(e->Sslots.p + GKs * (e->nblk + 1) * HMX_ROUND_SLOTS);
         if (hipHostMalloc(reinterpret_cast<void**>(&e->sync_host), 2 * sizeof(unsigned), hipHostMallocDefault) != hipSuccess) {
             rc = fail(HMX_ERR_HIP, "hipHostMalloc failed");
             break;
@@ -501,21 +527,9 @@ void hmx_destroy(hmx_engine* e) {
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     drain_spans(e);
     for (auto ev : e->pool) (void)hipEventDestroy(ev);
-    e->Zorig.release(); e->Zcos.release(); e->Zcorr.release(); e->R.release(); e->Y.release(); e->Yacc.release();
-    e->sigma.release(); e->theta.release(); e->Pr_b.release(); e->lamb.release(); e->rp.release(); e->lrp.release();
-    e->slab.release(); e->W.release(); e->group_cols.release(); e->s_cells.release(); e->s_tile_grp.release();
-    for (auto& L : e->lists) { L.cells.release(); L.tile_grp.release(); L.blk_start.release(); L.run_tiles.release(); }
-    e->ga_map.release();
     if (e->stream2) { (void)hipStreamSynchronize(e->stream2); (void)hipStreamDestroy(e->stream2); }
     if (e->pre_event) (void)hipEventDestroy(e->pre_event);
-    e->task_t0.release(); e->task_t1.release();
-    e->t3_t0.release(); e->t3_t1.release(); e->t3_stride.release(); e->t3_c0.release(); e->t3_cend.release(); e->t3_grp.release(); e->s_tile_start.release();
-    e->tile_blk[0].release(); e->tile_blk[1].release(); e->tile_blk_zero.release(); e->Osave.release(); e->Opriv.release(); e->Wf.release(); e->Yf.release(); e->Zcf.release();
-    e->task_grp.release(); e->gstart.release(); e->chunk_tab.release(); e->run_count.release(); e->run_start.release();
-    e->Ogrp.release(); e->ref_terms.release(); e->Tmass.release(); e->Ohist.release(); e->xch.release(); e->scratch.release();
-    e->cell_map.release(); e->cell_inv.release();
     for (auto ev : e->io_ev) if (ev) (void)hipEventDestroy(ev);
-    e->global_id.release(); e->wait_stats.release(); e->sync_words.p = nullptr; e->sync_words.n = 0; e->Sslots.release(); e->km_hn.release(); e->km_sums.release();
     if (e->sync_host) (void)hipHostFree(e->sync_host);
     comm_release(e);
     peer_release(e);
@@ -524,7 +538,7 @@ void hmx_destroy(hmx_engine* e) {
     if (e->obj_defer) (void)hipHostFree(e->obj_defer);
     if (e->sync_event) (void)hipEventDestroy(e->sync_event);
     if (e->stream) (void)hipStreamDestroy(e->stream);
-    delete e;
+    delete e;   // the device buffers free themselves
 }
 
 namespace {
@@ -658,7 +672,7 @@ int upload_impl(hmx_engine* e, const ZSource& z, const int32_t* static_cells, in
     // ridge tasks: runs of tiles of one group; with k_rtz2 a task is one workgroup's share, sized
     // for about four tasks per CU (k_rtz: one task per wave, <= 64 tiles)
     std::vector<int> t0, t1, tg;
-    const int CH = rtz2_ok(e->mt, e->dp) ? std::max(16, (n_static_tiles + 2 * e->rtz_wgs_per_cu * e->n_cus - 1) / (2 * e->rtz_wgs_per_cu * e->n_cus))
+    const int CH = rtz2_ok(e->mt, e->dp) ? std::max(16, (n_static_tiles + 2 * HMX_RTZ2_WGS_PER_CU * e->n_cus - 1) / (2 * HMX_RTZ2_WGS_PER_CU * e->n_cus))
                    : rtz_wide_ok(e->mt, e->dp) ? std::max(16, (n_static_tiles + 2 * e->n_cus - 1) / (2 * e->n_cus)) : 64;
     for (int i = 0; i < n_static_tiles;) {
         int j = i;
@@ -719,34 +733,24 @@ int upload_impl(hmx_engine* e, const ZSource& z, const int32_t* static_cells, in
             // cap of 2048 of round 5 they made 305 tasks on 256 CUs: a second, mostly idle round of workgroups, k_rtz3c 1 647 us for
             // 10 M cells against 124.5 us for 1 M.  A wave's fp32 accumulators then sum 512 tiles = 8 k cells before the fp64 fold.)
             int cap3 = one_per_cu ? 4096 : 256;
-            if (const char* tc = getenv("HMX_RTZ3_TASK_CAP")) cap3 = std::max(16, atoi(tc));   // (A/B runs)
+            if (e->rtz3_task_cap) cap3 = e->rtz3_task_cap;   // (A/B runs)
             const int CH3 = std::max(16, std::min(cap3, (n_static_tiles + target - 1) / target));
-            // HMX_RTZ3_TASKS=contig: a task is a contiguous run of a group's tiles; default: the m tasks of a group take
-            // neighbouring quads of tiles (task j: tiles ts + 4j + w + 4m i) and sweep the group's rows together
-            const char* tk = getenv("HMX_RTZ3_TASKS");
-            const bool interleave = !(tk && std::string(tk) == "contig");
+            // the m tasks of a group take neighbouring quads of tiles (task j: tiles ts + 4j + w + 4m i) and sweep the group's
+            // rows together (contiguous runs per task: +4 us per pass, interleaved tasks sweep neighbouring DRAM pages together)
             // tiles a workgroup takes side by side: k_rtz3's four waves own a tile each, k_rtz3c's eight; k_rtzw's waves share one
             e->rtz3_quad = rtz3_quad(e->mt, e->dp, e->nblk, e->Kp, e->allow_rtz_bf16);
             const int quad = rtz_wide_ok(e->mt, e->dp) ? 1 : e->rtz3_quad;
             for (int g = 0; g < e->G; ++g) {
                 const int ts = tstart[g], te = tstart[g + 1];
                 if (te <= ts) continue;
-                const int m = (te - ts + CH3 - 1) / CH3, per = (te - ts + m - 1) / m;
-                if (interleave) {
-                    const int mm = std::min(m, (te - ts + quad - 1) / quad);       // no task without a tile
-                    // (the group's first task holds the most tiles: the quads 0, mm, 2 mm, ... of the group's nq, the last one maybe short)
-                    const int nq = (te - ts + quad - 1) / quad, first = (nq + mm - 1) / mm;
-                    e->task3_tiles_max = std::max(e->task3_tiles_max, quad * first - ((nq - 1) % mm == 0 ? quad * nq - (te - ts) : 0));
-                    for (int j = 0; j < mm; ++j) {
-                        a0.push_back(ts + quad * j); a1.push_back(te); ag.push_back(g); ast.push_back(quad * mm);
-                        ac0.push_back(gs2[g] + quad * j * HMX_TILE); acend.push_back(gs2[g + 1]);
-                    }
-                    continue;
-                }
-                for (int i = ts; i < te; i += per) {
-                    e->task3_tiles_max = std::max(e->task3_tiles_max, std::min(i + per, te) - i);
-                    a0.push_back(i); a1.push_back(std::min(i + per, te)); ag.push_back(g); ast.push_back(quad);
-                    ac0.push_back(gs2[g] + (i - ts) * HMX_TILE); acend.push_back(gs2[g + 1]);
+                const int m = (te - ts + CH3 - 1) / CH3;
+                const int mm = std::min(m, (te - ts + quad - 1) / quad);       // no task without a tile
+                // (the group's first task holds the most tiles: the quads 0, mm, 2 mm, ... of the group's nq, the last one maybe short)
+                const int nq = (te - ts + quad - 1) / quad, first = (nq + mm - 1) / mm;
+                e->task3_tiles_max = std::max(e->task3_tiles_max, quad * first - ((nq - 1) % mm == 0 ? quad * nq - (te - ts) : 0));
+                for (int j = 0; j < mm; ++j) {
+                    a0.push_back(ts + quad * j); a1.push_back(te); ag.push_back(g); ast.push_back(quad * mm);
+                    ac0.push_back(gs2[g] + quad * j * HMX_TILE); acend.push_back(gs2[g + 1]);
                 }
             }
             e->ntasks3 = (int)a0.size();
@@ -854,10 +858,6 @@ int lisi_impl(int32_t device_id, const LisiSource& src, int64_t n, int32_t d, co
     DevBuf<float> X32, cn;
     DevBuf<unsigned long long> lists;
     DevBuf<int> counts, labels, ki;
-    struct Release {
-        DevBuf<double>&a, &b, &c, &d2; DevBuf<float>&f, &g; DevBuf<unsigned long long>&h; DevBuf<int>&i, &j, &k;
-        ~Release() { a.release(); b.release(); c.release(); d2.release(); f.release(); g.release(); h.release(); i.release(); j.release(); k.release(); }
-    } guard{X64, sums, out, kd, X32, cn, lists, counts, labels, ki};
     int rc;
     if ((rc = X64.reserve((size_t)n * d)) || (rc = sums.reserve(d)) || (rc = X32.reserve((size_t)npad * dp)) || (rc = cn.reserve(npad)) ||
         (rc = lists.reserve((size_t)npad * cap)) || (rc = counts.reserve(n)) || (rc = labels.reserve((size_t)n * n_labels)))
@@ -892,7 +892,6 @@ int lisi_impl(int32_t device_id, const LisiSource& src, int64_t n, int32_t d, co
         const double waves = (double)npad / 64.0, tiles = (double)((n + 15) / 16);
         fprintf(stderr, "[lisi prof] cycles per tile per wave: loads-issue %.0f, fragments+MFMA %.0f, store pieces (load wait) %.0f, append %.0f, barrier %.0f\n",
                 h[0] / waves / tiles, h[1] / waves / tiles, h[2] / waves / tiles, h[3] / waves / tiles, h[4] / waves / tiles);
-        prof.release();
     }
 #endif
     LisiFinishArgs fa{};
@@ -1025,10 +1024,6 @@ int hmx_knn_predict(int32_t device_id, const void* Q, int q_dtype, int64_t n_q, 
     DevBuf<float> Q32, R32, cn;
     DevBuf<unsigned long long> lists;
     DevBuf<int> counts, labels;
-    struct Release {
-        DevBuf<double>&a, &b, &c, &d2; DevBuf<float>&f, &g, &h; DevBuf<unsigned long long>&i; DevBuf<int>&j, &k2;
-        ~Release() { a.release(); b.release(); c.release(); d2.release(); f.release(); g.release(); h.release(); i.release(); j.release(); k2.release(); }
-    } guard{Q64, R64, qsums, rsums, Q32, R32, cn, lists, counts, labels};
     if ((rc = Q64.reserve((size_t)n_q * d)) || (rc = R64.reserve((size_t)n_r * d)) || (rc = qsums.reserve(d)) || (rc = rsums.reserve(d)) ||
         (rc = Q32.reserve((size_t)nq_pad * dp)) || (rc = R32.reserve((size_t)nr_pad * dp)) || (rc = cn.reserve(nr_pad)) ||
         (rc = lists.reserve((size_t)S * nq_pad * cap)) || (rc = counts.reserve((size_t)S * n_q)) ||
@@ -1068,7 +1063,6 @@ int hmx_kmeans_seed(hmx_engine* e, const float* points, int64_t n_points, uint64
                  bCenters = up((size_t)K * d * 4), bChunk = up((size_t)nchunks * 8), bPots = up((size_t)K * HMX_SEED_SLOTS * 8),
                  bCand = up((size_t)K * HMX_SEED_SLOTS * 4), bChosen = up((size_t)K * 4);
     DevBuf<unsigned char> arena;
-    struct Release { DevBuf<unsigned char>& a; ~Release() { a.release(); } } guard{arena};
     if ((rc = arena.reserve(2 * bX + bClosest + bMin + bCenters + bChunk + bPots + bCand + bChosen))) return rc;
     unsigned char* cur = arena.p;
     auto take = [&](size_t bytes) { unsigned char* p = cur; cur += bytes; return p; };
@@ -1254,7 +1248,7 @@ static int centroid_pass(hmx_engine* e) {
     const bool rtz2 = rtz2_ok(e->mt, e->dp);
     const bool rtzw = !rtz2 && rtz_wide_ok(e->mt, e->dp);
     const int n_tiles = e->n_s_tiles;
-    const int wgs = rtz2 ? std::min(e->rtz_wgs_per_cu * e->n_cus, std::max(1, (n_tiles + 7) / 8))
+    const int wgs = rtz2 ? std::min(HMX_RTZ2_WGS_PER_CU * e->n_cus, std::max(1, (n_tiles + 7) / 8))
                   : rtzw ? std::min(e->n_cus, std::max(1, (n_tiles + 7) / 8))
                          : std::min(256, std::max(1, (n_tiles + 31) / 32));
     if ((rc = e->slab.reserve(rtz2 ? (size_t)wgs * rtz2_slab_floats(e->mt, e->dp)
@@ -1547,7 +1541,7 @@ static int round_body(hmx_engine* e, int flags, int n_tiles_upper, const std::ve
         rtz_geometry(e->mt, e->ntd, &nsub, &spw);
         const bool rtz2 = rtz2_ok(e->mt, e->dp) && e->round_mode == 1;
         const bool rtzw = !rtz2 && rtz_wide_ok(e->mt, e->dp);
-        int wgs = rtz2 ? std::min(e->rtz_wgs_per_cu * e->n_cus, std::max(1, (n_tiles_upper + 7) / 8))
+        int wgs = rtz2 ? std::min(HMX_RTZ2_WGS_PER_CU * e->n_cus, std::max(1, (n_tiles_upper + 7) / 8))
                   : rtzw ? std::min(e->n_cus, std::max(1, (n_tiles_upper + 7) / 8))
                          : std::min(256, std::max(1, (n_tiles_upper + 31) / 32));
         if ((rc = e->slab.reserve(rtz2 ? (size_t)wgs * rtz2_slab_floats(e->mt, e->dp)
@@ -1605,7 +1599,7 @@ static int round_body(hmx_engine* e, int flags, int n_tiles_upper, const std::ve
             ra.cells = e->lists[e->cur].cells.p; ra.tile_grp = e->lists[e->cur].tile_grp.p; ra.blk_start = e->lists[e->cur].blk_start.p;
             ra.O_start = e->Ogrp.p; ra.S_old = e->Sold; ra.S_new = e->Sslots.p; ra.O_out = e->Ogrp.p; ra.T_out = e->Tmass.p;
             ra.obj = e->objacc; ra.group_cols = e->group_cols.p; ra.Pr_b = e->Pr_b.p; ra.theta = e->theta.p;
-            ra.counter = e->sync_words.p; ra.error = e->sync_words.p + 1; ra.wait_stats = e->wait_stats.p;
+            ra.counter = e->sync_words; ra.error = e->sync_words + 1; ra.wait_stats = e->wait_stats.p;
             ra.K = e->K; ra.Kp = e->Kp; ra.K16 = e->K16; ra.dp = e->dp; ra.ldy = e->ldy; ra.G = e->G; ra.B = e->B; ra.V = e->V;
             ra.nblk = e->nblk; ra.spin_limit = e->spin_limit;
             ra.frozen = e->frozen();
@@ -1613,7 +1607,7 @@ static int round_body(hmx_engine* e, int flags, int n_tiles_upper, const std::ve
                 // row-request placement of the group-affine sweep (k_round, tile_step): measured per shape, HMX_ROUND_REQ overrides
                 ra.req_mode = e->ga_per_wg > HMX_ROUND_GA_TILES ? 1 : e->ga_nwg > 32 ? 2 : 0;
                 ra.ga_slots = e->ga_nwg > 32 ? 2 : 1;
-                if (const char* rq = getenv("HMX_ROUND_REQ")) ra.req_mode = std::max(0, std::min(2, atoi(rq)));
+                if (e->round_req >= 0) ra.req_mode = e->round_req;
             }
             if (ga) { ra.ga = 1; ra.run_start = e->lists[e->cur].run_tiles.p; ra.wg_map = e->ga_map.p; e->n_sweeps_ga++; }
             if (e->n_sweep_launches++ == e->test_fail_sweep) ra.spin_limit = 0;
@@ -1624,11 +1618,18 @@ static int round_body(hmx_engine* e, int flags, int n_tiles_upper, const std::ve
                 e->round_epoch += 256;   // (> HMX_MAX_BLOCKS: the flag values of two launches never meet)
             }
 #ifdef HMX_ROUND_PROF
-            static DevBuf<unsigned long long> prof;
+            static unsigned long long* prof = nullptr;   // leaked on purpose: a static destructor would free it after the runtime may be gone
+            static size_t prof_n = 0;
             static int prof_rounds = 0;
-            if (prof.reserve((size_t)wgs * e->nblk * 32)) return -1;
-            (void)hipMemsetAsync(prof.p, 0, (size_t)wgs * e->nblk * 32 * 8, e->stream);
-            ra.prof = prof.p;
+            if ((size_t)wgs * e->nblk * 32 > prof_n) {
+                if (prof) (void)hipFree(prof);
+                prof = nullptr;
+                prof_n = 0;
+                if (hipMalloc(reinterpret_cast<void**>(&prof), (size_t)wgs * e->nblk * 32 * 8) != hipSuccess) return -1;
+                prof_n = (size_t)wgs * e->nblk * 32;
+            }
+            (void)hipMemsetAsync(prof, 0, (size_t)wgs * e->nblk * 32 * 8, e->stream);
+            ra.prof = prof;
 #endif
             const bool extra_tiles = ga ? e->ga_extra : max_upper > 16 * wgs;   // (ROUND_TPW x ROUND_WAVES slots per workgroup; group-affine: 14 per workgroup of the run's group)
             if (launch_round(ra, e->mt, multi ? wgs + 1 : wgs, e->stream, extra_tiles, e->allow_round_bf16)) return fail(HMX_ERR_ARG, "unsupported shape for k_round");
@@ -1638,7 +1639,7 @@ static int round_body(hmx_engine* e, int flags, int n_tiles_upper, const std::ve
             if (++prof_rounds == 25) {   // one round in steady state: phase durations over workgroups and blocks
                 std::vector<unsigned long long> h((size_t)wgs * e->nblk * 32);
                 (void)hipStreamSynchronize(e->stream);
-                (void)hipMemcpy(h.data(), prof.p, h.size() * 8, hipMemcpyDeviceToHost);
+                (void)hipMemcpy(h.data(), prof, h.size() * 8, hipMemcpyDeviceToHost);
                 const char* names[5] = {"wait", "table", "post", "flush+arrive", "pre(next)"};
                 for (int ph = 0; ph < 5; ++ph) {
                     double sum = 0, mx = 0;
@@ -2091,12 +2092,12 @@ int hmx_peer_selftest(hmx_engine* e) {
     if (!e->peers_attached) return fail(HMX_ERR_STATE, "hmx_peer_attach must come first");
     int rc;
     if ((rc = use_device(e))) return rc;
-    HIP_TRY(hipMemsetAsync(e->sync_words.p, 0, 2 * sizeof(unsigned), e->stream));
+    HIP_TRY(hipMemsetAsync(e->sync_words, 0, 2 * sizeof(unsigned), e->stream));
     e->selftest_token += 1;
     int iters = 8;                                      // HMX_PEER_SELFTEST_ITERS: a soak (tests), at most 65535 cycles
     if (const char* it = getenv("HMX_PEER_SELFTEST_ITERS")) iters = std::max(1, std::min(65535, atoi(it)));
-    launch_peer_selftest(e->peer_dev.p, e->box, e->n_ranks, e->rank, (size_t)(e->G + 1) * e->K16, e->selftest_token, iters, e->sync_words.p, e->stream);
-    HIP_TRY(hipMemcpyAsync(e->sync_host, e->sync_words.p, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, e->stream));
+    launch_peer_selftest(e->peer_dev.p, e->box, e->n_ranks, e->rank, (size_t)(e->G + 1) * e->K16, e->selftest_token, iters, e->sync_words, e->stream);
+    HIP_TRY(hipMemcpyAsync(e->sync_host, e->sync_words, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipGetLastError());
     return e->sync_host[0] == 1u ? 1 : 0;
@@ -2323,15 +2324,13 @@ int hmx_get_rows(hmx_engine* e, int which, const int32_t* rows, int32_t n_rows, 
     if ((rc = use_device(e))) return rc;
     DevBuf<int> d_rows;
     DevBuf<float> d_out;
-    if ((rc = d_rows.reserve(n_rows)) || (rc = d_out.reserve((size_t)n_rows * cols))) { d_rows.release(); d_out.release(); return rc; }
+    if ((rc = d_rows.reserve(n_rows)) || (rc = d_out.reserve((size_t)n_rows * cols))) return rc;
     hipError_t he = hipMemcpyAsync(d_rows.p, rows, (size_t)n_rows * sizeof(int), hipMemcpyHostToDevice, e->stream);
     if (he == hipSuccess) {
         launch_gather_rows((const float*)p, ld, cols, d_rows.p, n_rows, d_out.p, e->stream);
         he = hipMemcpyAsync(host_out, d_out.p, bytes, hipMemcpyDeviceToHost, e->stream);
     }
     if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-    d_rows.release();
-    d_out.release();
     if (he != hipSuccess) return fail(HMX_ERR_HIP, "hmx_get_rows: %s", hipGetErrorString(he));
     return HMX_OK;
 }
@@ -2512,17 +2511,16 @@ int hmx_cluster_moments(hmx_engine* e, int which_Z, const int32_t* codes, int32_
     int64_t chunk1, chunk2;
     const int C1 = score_chunks(e->N, n_sums * sizeof(double), (size_t)64 << 20, 2048, &chunk1);
     const int C2 = score_chunks(e->N, n_tiles * sizeof(double), (size_t)256 << 20, 4096, &chunk2);
-    DevBuf<int> d_codes;
-    DevBuf<double> slab1, sums, meanb, slab2, tiles;
-    auto release = [&]() { d_codes.release(); slab1.release(); sums.release(); meanb.release(); slab2.release(); tiles.release(); };
     std::vector<double> h_sums(n_sums), h_tiles(n_tiles);
-    auto run = [&]() -> int {
-        int r;
-        if ((r = slab1.reserve(n_sums * C1)) || (r = sums.reserve(n_sums)) || (r = meanb.reserve((size_t)a.G16 * 16 * dt)) ||
-            (r = slab2.reserve(n_tiles * C2)) || (r = tiles.reserve(n_tiles)))
-            return r;
+    {
+        DevBuf<int> d_codes;
+        DevBuf<double> slab1, sums, meanb, slab2, tiles;
+        SyncOnExit sync{e->stream};
+        if ((rc = slab1.reserve(n_sums * C1)) || (rc = sums.reserve(n_sums)) || (rc = meanb.reserve((size_t)a.G16 * 16 * dt)) ||
+            (rc = slab2.reserve(n_tiles * C2)) || (rc = tiles.reserve(n_tiles)))
+            return rc;
         if (codes) {
-            if ((r = d_codes.reserve(e->N))) return r;
+            if ((rc = d_codes.reserve(e->N))) return rc;
             HIP_TRY(hipMemcpyAsync(d_codes.p, codes, (size_t)e->N * sizeof(int), hipMemcpyHostToDevice, e->stream));
         }
         a.codes = d_codes.p; a.slab1 = slab1.p; a.sums = sums.p; a.mean = meanb.p; a.slab2 = slab2.p; a.tiles = tiles.p;
@@ -2535,12 +2533,7 @@ int hmx_cluster_moments(hmx_engine* e, int which_Z, const int32_t* codes, int32_
         HIP_TRY(hipMemcpyAsync(h_sums.data(), sums.p, n_sums * sizeof(double), hipMemcpyDeviceToHost, e->stream));
         HIP_TRY(hipMemcpyAsync(h_tiles.data(), tiles.p, n_tiles * sizeof(double), hipMemcpyDeviceToHost, e->stream));
         HIP_TRY(hipStreamSynchronize(e->stream));
-        return 0;
-    };
-    rc = run();
-    if (rc) (void)hipStreamSynchronize(e->stream);
-    release();
-    if (rc) return rc;
+    }
     const double nan = std::nan("");
     for (int g = 0; g < G; ++g) {
         const double m = h_sums[(size_t)g * a.ld1 + 16 * dt], m2 = h_sums[(size_t)g * a.ld1 + 16 * dt + 1];
@@ -2597,38 +2590,31 @@ int hmx_mapping_score(hmx_engine* e, int which_Z, const double* whitening, const
     }
     if ((rc = use_device(e))) return rc;
     DevBuf<double> dT, dOff, dOut;
-    auto release = [&]() { dT.release(); dOff.release(); dOut.release(); };
+    SyncOnExit sync{e->stream};
     hipStream_t caller = static_cast<hipStream_t>(stream);
-    auto run = [&]() -> int {
-        int r;
-        if ((r = dT.reserve(P.size())) || (r = dOff.reserve(off.size()))) return r;
-        if (score_host && (r = dOut.reserve(e->N))) return r;
-        if (score_device) {
-            if ((r = io_events(e))) return r;
-            HIP_TRY(hipEventRecord(e->io_ev[0], caller));           // the destination may still be in use on the caller's stream
-            HIP_TRY(hipStreamWaitEvent(e->stream, e->io_ev[0], 0));
-        }
-        HIP_TRY(hipMemcpyAsync(dT.p, P.data(), P.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(dOff.p, off.data(), off.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
-        MScoreArgs a{};
-        a.R = e->R.p; a.Z = Z; a.map = e->cell_map.p; a.T = dT.p; a.off = dOff.p;
-        a.out = score_host ? dOut.p : static_cast<double*>(score_device);
-        a.N = e->N; a.K = K; a.Kp = e->Kp; a.dp = e->dp; a.d = d; a.dt = dt;
-        launch_mscore(a, e->stream);
-        HIP_TRY(hipGetLastError());
-        if (score_host) {
-            HIP_TRY(hipMemcpyAsync(score_host, dOut.p, (size_t)e->N * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-        } else {
-            HIP_TRY(hipEventRecord(e->io_ev[1], e->stream));        // the caller's later work sees the scores
-            HIP_TRY(hipStreamWaitEvent(caller, e->io_ev[1], 0));
-        }
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        return 0;
-    };
-    rc = run();
-    if (rc) (void)hipStreamSynchronize(e->stream);
-    release();
-    return rc ? rc : HMX_OK;
+    if ((rc = dT.reserve(P.size())) || (rc = dOff.reserve(off.size()))) return rc;
+    if (score_host && (rc = dOut.reserve(e->N))) return rc;
+    if (score_device) {
+        if ((rc = io_events(e))) return rc;
+        HIP_TRY(hipEventRecord(e->io_ev[0], caller));           // the destination may still be in use on the caller's stream
+        HIP_TRY(hipStreamWaitEvent(e->stream, e->io_ev[0], 0));
+    }
+    HIP_TRY(hipMemcpyAsync(dT.p, P.data(), P.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(dOff.p, off.data(), off.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    MScoreArgs a{};
+    a.R = e->R.p; a.Z = Z; a.map = e->cell_map.p; a.T = dT.p; a.off = dOff.p;
+    a.out = score_host ? dOut.p : static_cast<double*>(score_device);
+    a.N = e->N; a.K = K; a.Kp = e->Kp; a.dp = e->dp; a.d = d; a.dt = dt;
+    launch_mscore(a, e->stream);
+    HIP_TRY(hipGetLastError());
+    if (score_host) {
+        HIP_TRY(hipMemcpyAsync(score_host, dOut.p, (size_t)e->N * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    } else {
+        HIP_TRY(hipEventRecord(e->io_ev[1], e->stream));        // the caller's later work sees the scores
+        HIP_TRY(hipStreamWaitEvent(caller, e->io_ev[1], 0));
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return HMX_OK;
 }
 
 }  // extern "C"

@@ -24,7 +24,7 @@ struct AssignArgs {
     int blk;
     int tile_begin, tile_end;  // host-side range (or an upper bound of its length when blk_start)
     int K, Kp, K16, mt, dp, ldy;
-    int G, ldy_lds, tables_in_lds, tiles_per_wave, ablate;
+    int G, ldy_lds, tables_in_lds;
     const unsigned* Yf;    // wide shapes, bf16 pipe: Y as the A fragments of k_assign_wide3 (launch_y_planes), or null (the f32-input kernel k_assign_wide)
     int bf16_pipe;         // wide shapes: the bf16-pipe instance k_assign_wide3 (0: engines created under HMX_ROUND_F32=1 keep k_assign_wide)
     // k_assign_wide3 building the block's table itself (assign_wide3_fuses_table; one batch variable): O_b = O_prev + S_add - S_sub
@@ -46,9 +46,7 @@ struct AssignArgs {
                            // assignment of the device k-means (a one-hot row of R per cell) instead of the softmax; null otherwise
 };
 
-#ifndef HMX_ROUND_SLOTS
 #define HMX_ROUND_SLOTS 4 /* k_round: a block's new sums are spread over this many fp64 tables (2 and 8 measured in round 6: profiles/r06_ab_k_round_slots_poll.txt) */
-#endif
 
 // One whole update_R sweep (all blocks) in one persistent launch (k_round).
 struct RoundArgs {

@@ -314,9 +314,6 @@ __device__ __forceinline__ float fast_exp(float x) {
 }
 
 #define ASSIGN_WAVES 8
-#ifndef HMX_ABL
-#define HMX_ABL 0   /* timing experiments only: 1 no block sums, 2 no R store, 4 cheap math, 8 no GEMM, 16 no tile loop, 32 no gather */
-#endif
 
 template <int MT, bool PENALTY>
 __global__ __launch_bounds__(64 * ASSIGN_WAVES, 4) void k_assign_lds(AssignArgs a) {
@@ -387,12 +384,12 @@ __global__ __launch_bounds__(64 * ASSIGN_WAVES, 4) void k_assign_lds(AssignArgs 
     __syncthreads();
 
     double km_d = 0.0, ent_d = 0.0;
-    if (has_tile && !(HMX_ABL & 16)) {
+    if (has_tile) {
         // ---- distance GEMM: C[cluster][cell] = Y . Zcos^T over the PC dimension ------------
         f32x4 acc[MT];
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) acc[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        for (int kb = 0; kb < ((HMX_ABL & 8) ? 0 : kb_full); ++kb) {
+        for (int kb = 0; kb < kb_full; ++kb) {
             const f32x4 zb = ld4(Zt + (size_t)c16 * LDY + 16 * kb + 4 * q);
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
@@ -401,7 +398,7 @@ __global__ __launch_bounds__(64 * ASSIGN_WAVES, 4) void k_assign_lds(AssignArgs 
                 for (int i = 0; i < 4; ++i) acc[mt] = MFMA16(ya[i], zb[i], acc[mt]);
             }
         }
-        for (int s = 0; s < ((HMX_ABL & 8) ? 0 : tail); ++s) {
+        for (int s = 0; s < tail; ++s) {
             const int col = 16 * kb_full + 4 * s + q;
             const float zb = Zt[(size_t)c16 * LDY + col];
 #pragma unroll
@@ -422,7 +419,7 @@ __global__ __launch_bounds__(64 * ASSIGN_WAVES, 4) void k_assign_lds(AssignArgs 
                 const float dist = 2.f * (1.f - acc[mt][r]);   // :380 / :447
                 const float arg = dist * ni[r];                // :383 / :466   -dist / sigma
                 acc[mt][r] = arg;
-                e1 += (HMX_ABL & 4) ? arg * 0.001f + 1.0f : fast_exp(arg);   // :384 / :467
+                e1 += fast_exp(arg);   // :384 / :467
             }
         }
         e1 = wave_sum_q(e1);                                   // column sum of :385 / :468
@@ -437,7 +434,7 @@ __global__ __launch_bounds__(64 * ASSIGN_WAVES, 4) void k_assign_lds(AssignArgs 
                 const f32x4 pw = ld4(rp + 16 * mt + 4 * q);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float ex = (HMX_ABL & 4) ? acc[mt][r] * 0.001f + 1.0f : fast_exp(acc[mt][r]);
+                    const float ex = fast_exp(acc[mt][r]);
                     us += (ex * inv_e1) * pw[r];               // :468 then :500
                 }
             }
@@ -463,7 +460,7 @@ __global__ __launch_bounds__(64 * ASSIGN_WAVES, 4) void k_assign_lds(AssignArgs 
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float arg = acc[mt][r];
-                const float ex = (HMX_ABL & 4) ? arg * 0.001f + 1.0f : fast_exp(arg);
+                const float ex = fast_exp(arg);
                 float Rv = PENALTY ? ((ex * inv_e1) * pw[r]) * inv_u1 : ex * inv_e1;   // :503 / :385
                 Rv = live ? Rv : 0.f;
                 rv[r] = Rv;
@@ -473,16 +470,14 @@ __global__ __launch_bounds__(64 * ASSIGN_WAVES, 4) void k_assign_lds(AssignArgs 
                 ent += pos ? sg[r] * (Rv * logR) : 0.f;        // sigma R log R    (:402)
             }
             const int col = 16 * mt + 4 * q;
-            if (live && col < a.Kp && !(HMX_ABL & 2)) st4(rrow + col, rv);
+            if (live && col < a.Kp) st4(rrow + col, rv);
             // block sums of the new R (:506-507): 16-cell DPP reduction, one fp64 add per (group, cluster)
-            if (!(HMX_ABL & 1)) {
-                f32x4 ss;
+            f32x4 ss;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) ss[r] = row16_sum(rv[r]);
-                if (c16 == 0) {
+            for (int r = 0; r < 4; ++r) ss[r] = row16_sum(rv[r]);
+            if (c16 == 0) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) atomicAdd(sdst + col + r, (double)ss[r]);
-                }
+                for (int r = 0; r < 4; ++r) atomicAdd(sdst + col + r, (double)ss[r]);
             }
         }
         km_d = wave_sum_all((double)km);
@@ -538,9 +533,6 @@ __global__ __launch_bounds__(64 * ASSIGN_WAVES, 4) void k_assign_lds(AssignArgs 
 // Waits are bounded: a workgroup that is not resident would otherwise hang the grid; on timeout
 // a.error is set and the host reports it.
 // ------------------------------------------------------------------------------------------
-#ifndef HMX_RABL
-#define HMX_RABL 0   /* timing experiments only: 1 no block sums, 2 no R store, 4 no exp in round_post */
-#endif
 #ifdef HMX_ROUND_PROF   /* timing experiments only: per-workgroup phase stamps (s_memtime) */
 #define RSTAMP(slot) do { if (tid == 0 && a.prof) a.prof[((size_t)wg * a.nblk + b) * 32 + (slot)] = __builtin_amdgcn_s_memtime(); } while (0)
 #define TSTAMP(slot) do { if (tid == 0 && a.prof && prof_b >= 0) a.prof[((size_t)wg * a.nblk + prof_b) * 32 + (slot)] = __builtin_amdgcn_s_memtime(); } while (0)
@@ -585,20 +577,17 @@ __device__ __forceinline__ void round_issue_z(const float* __restrict__ Zcos, in
 }
 
 // table-independent half of a tile: distance GEMM against the LDS-resident centroids -> exponent arguments.
-// LOG2 (k_round): the centroid rows in LDS are pre-scaled by c_k = 2 log2(e) / sigma_k and `nis` holds -c_k, so the
+// The centroid rows in LDS are pre-scaled by c_k = 2 log2(e) / sigma_k and `nis` holds -c_k, so the
 // accumulators START at -c_k and the products land directly on  -dist / sigma * log2(e) = c_k (y.z - 1)  -- the argument of
 // the hardware exp2 (:447, :466) -- and the three VALU operations per entry of the conversion are gone.  The rounding of
 // the scaled dot product (magnitudes up to c_k ~ 29: 2e-6 absolute in the argument) is what 2 (1 - y.z) / sigma carried
 // already (the rounding of y.z, 1e-7, times 2 / sigma).
-#ifndef HMX_ROUND_EXP2
-#define HMX_ROUND_EXP2 1
-#endif
-template <int MT, int KS, bool LOG2 = false>
+template <int MT, int KS>
 __device__ __forceinline__ void round_compute(const float* Ys, const float* nis, int LDY, int c16, int q,
                                               const RoundZ<KS>& Z, RoundTile<MT>& T) {
     constexpr int NF = KS / 4, NT = KS % 4;
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt) T.arg[mt] = LOG2 ? ld4(nis + 16 * mt + 4 * q) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int mt = 0; mt < MT; ++mt) T.arg[mt] = ld4(nis + 16 * mt + 4 * q);
 #pragma unroll
     for (int j = 0; j < NF; ++j) {
 #pragma unroll
@@ -615,14 +604,6 @@ __device__ __forceinline__ void round_compute(const float* Ys, const float* nis,
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) T.arg[mt] = MFMA16(Ys[(size_t)(16 * mt + c16) * LDY + col], Z.zt[s], T.arg[mt]);
     }
-    if (!LOG2) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            const f32x4 ni = ld4(nis + 16 * mt + 4 * q);
-            const f32x4 one = (f32x4){1.f, 1.f, 1.f, 1.f};
-            T.arg[mt] = (2.f * (one - T.arg[mt])) * ni;          // dist = 2 (1 - Y.Z) (:447), arg = -dist / sigma (:466)
-        }
-    }
 }
 
 // ---- the same distance GEMM on the bf16 matrix pipe, fp32 operands as three bf16 terms (hmx_device.h) -------------
@@ -631,9 +612,6 @@ __device__ __forceinline__ void round_compute(const float* Ys, const float* nis,
 // of 16 NS + 4 registers (the odd multiple of 4 spreads a 16-lane group's 16-byte reads over all 64 banks); the cells' rows
 // are split in registers when their fragments are read -- 9 vector instructions per pair of values, next to six
 // 16-cycle MFMAs per cluster tile and k-step where the f32-input form took eight 32-cycle ones.
-#ifndef HMX_ROUND_BF3
-#define HMX_ROUND_BF3 1
-#endif
 constexpr int bf3_steps(int KS) { return (KS + 7) / 8; }
 constexpr int bf3_ldb(int KS) { return 16 * bf3_steps(KS) + 4; }   // row stride of a plane, in 32-bit words
 // Row requests of the bf16-pipe instances: one LDS-DMA request brings WHOLE rows -- 64 / KS of them, lane l the piece l % KS
@@ -694,7 +672,7 @@ __device__ __forceinline__ void round_raw_pieces(const float* zr, int q, f32x4 (
             }
         }
 }
-// Yb: the three planes, K16 x bf3_ldb(KS) words each; nis: the accumulators' start (-c_k), see round_compute<.., true>
+// Yb: the three planes, K16 x bf3_ldb(KS) words each; nis: the accumulators' start (-c_k), see round_compute
 template <int MT, int KS>
 __device__ __forceinline__ void round_compute_bf3(const unsigned* Yb, const float* nis, int c16, int q,
                                                   const RoundZ3<KS>& Z, RoundTile<MT>& T) {
@@ -812,17 +790,11 @@ __device__ __forceinline__ void round_rows_from_lds(const float* zt, int c16, in
 // Padded clusters carry arg = -120 (exp underflows to an exact 0) and sigma 0.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// LOG2: the arguments are in log2 units (round_compute<.., true>): one v_exp_f32 per entry, the sum of t sigma arg is scaled
+// LOG2: the arguments are in log2 units (round_compute): one v_exp_f32 per entry, the sum of t sigma arg is scaled
 // by ln 2 once per tile.  A2TAB: the term  sum t sigma log(ratio^theta)  is NOT accumulated here -- summed over the cells of a
 // block it equals  sum_(g,k) log(ratio^theta)[g][k] sigma_k S[g][k]  with S the block sums of the new R that the caller
 // keeps anyway (k_round adds it when it publishes them): one fma per entry and the log table's reads are gone.
-#ifndef HMX_ROUND_A2TAB
-#define HMX_ROUND_A2TAB 1
-#endif
-#ifndef HMX_ROUND_PK
-#define HMX_ROUND_PK 1
-#endif
-template <int MT, bool PENALTY = true, bool LOG2 = false, bool A2TAB = false, bool PK = (HMX_ROUND_PK != 0)>
+template <int MT, bool PENALTY = true, bool LOG2 = false, bool A2TAB = false, bool PK = true>
 __device__ __forceinline__ void round_post_pass1(const float* sig, const float* rpT, const float* lrpT, int q,
                                                  RoundTile<MT>& T, float& scl, double& km_acc, double& ent_acc) {
     constexpr int K16 = 16 * MT;
@@ -864,11 +836,7 @@ __device__ __forceinline__ void round_post_pass1(const float* sig, const float* 
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float arg = T.arg[mt][r];
-#if HMX_RABL & 4
-            const float ex = arg * 0.001f + 1.0f;
-#else
             const float ex = LOG2 ? __builtin_amdgcn_exp2f(arg) : fast_exp_finite(arg);           // :467
-#endif
             e1 += ex;
             const float t = ex * pw[r];                      // :500 (the 1/e1 of :468 cancels, see above)
             const float ts = t * sg[r];
@@ -891,29 +859,17 @@ __device__ __forceinline__ void round_post_pass1(const float* sig, const float* 
 // second pass for the two tiles a wave carries: R rows out, sums over the 16 cells of a tile into
 // the block's (group, cluster) table.  Tiles of one group (the usual case: a wave's tiles are
 // neighbours in the block's group-sorted list) share one cross-lane reduction.
-#ifndef HMX_ROUND_RETURNING
-/* 1 (default): the slot atomics of k_round (and the peer-box writes of its gateway workgroup) RETURN their old value, so the
+/* The slot atomics of k_round (and the peer-box writes of its gateway workgroup) RETURN their old value, so the
    wave's vmcnt(0) before the arrival means "performed", not "accepted".  The persistent wide sweep of round 3 showed what the difference
    can be: a flag raised behind non-returning atomics or stores was seen by other XCDs before some of the data.  k_round queues
    at most two atomics per thread and never showed it in any parity run, but "never observed" is not an ordering guarantee.
    Measured cost at C3: 3.67 -> 3.75 ms of sweeps per Harmony iteration (+2 %). */
-#define HMX_ROUND_RETURNING 1
-#endif
 // Sums of NV = 4 MT per-lane values over the 16 lanes of each DPP row (the 16 cells of a tile; a row = one q), delivered
 // SCATTERED: lane c16 ends up with the total of value bitrev4(c16) of each group of 16 values.  Four butterfly stages; in
 // stage s a lane keeps one value of every pair and hands the other to its partner -- row_mirror / row_half_mirror /
 // quad_perm [3,2,1,0] / quad_perm [1,0,3,2], each keeping the bits the earlier stages decided on -- so 16 values cost
 // 8 + 4 + 2 + 1 pairs x (2 selects + 1 DPP add) = 45 operations instead of 16 x 5 for sixteen full row sums, and the
 // result is one value per lane: ONE conversion and ONE fp64 LDS add per group of 16 clusters and wave instead of 16 x 4.
-#ifndef HMX_ROUND_RS
-#define HMX_ROUND_RS 1
-#endif
-#ifndef HMX_ROUND_R_NT
-#define HMX_ROUND_R_NT 0
-#endif
-#ifndef HMX_ROUND_PUBWAVE
-#define HMX_ROUND_PUBWAVE 1
-#endif
 template <int N>
 __device__ __forceinline__ float rs16(const float (&v)[N], int c16) {   // N <= 16 live values, the rest count as zero
     static_assert(N >= 1 && N <= 16, "group of 16");
@@ -978,7 +934,6 @@ __device__ __forceinline__ void round_post_pass2(float* R, int Kp, double* Sd, i
     double* sd0 = Sd + (size_t)T0.grp * K16;
     double* sd1 = Sd + (size_t)T1.grp * K16;
     if (!has1) scl1 = 0.f;
-#if HMX_ROUND_RS
     // four cluster tiles at a time: R rows out, then the group's 16 values per lane summed over the cells (:506-507)
     auto group = [&](auto nm_c, int g) {
         constexpr int NM = decltype(nm_c)::value;
@@ -988,17 +943,9 @@ __device__ __forceinline__ void round_post_pass2(float* R, int Kp, double* Sd, i
             const int mt = 4 * g + m, col = 16 * mt + 4 * q;
             rv0[m] = T0.arg[mt] * scl0;                    // :503
             rv1[m] = T1.arg[mt] * scl1;
-#if !(HMX_RABL & 2)
-#if HMX_ROUND_R_NT   /* (experiment of round 6: the R rows are written once per round and read once by the next pass -- streaming stores) */
-            if (live0 && col < Kp) __builtin_nontemporal_store(rv0[m], reinterpret_cast<f32x4*>(row0 + col));
-            if (live1 && col < Kp) __builtin_nontemporal_store(rv1[m], reinterpret_cast<f32x4*>(row1 + col));
-#else
             if (STORE0 && live0 && col < Kp) st4(row0 + col, rv0[m]);
             if (live1 && col < Kp) st4(row1 + col, rv1[m]);
-#endif
-#endif
         }
-#if !(HMX_RABL & 1)
         if (joint || !has1) {                              // one table row for both tiles (scl1 == 0 without a second tile)
 #pragma unroll
             for (int m = 0; m < NM; ++m) rv0[m] += rv1[m];
@@ -1007,49 +954,10 @@ __device__ __forceinline__ void round_post_pass2(float* R, int Kp, double* Sd, i
             block_sums_rs<NM>(rv0, sd0 + 64 * g, c16, q);
             block_sums_rs<NM>(rv1, sd1 + 64 * g, c16, q);
         }
-#endif
     };
 #pragma unroll
     for (int g = 0; g < MT / 4; ++g) group(std::integral_constant<int, 4>{}, g);
     if constexpr (MT % 4 != 0) group(std::integral_constant<int, (MT % 4 ? MT % 4 : 1)>{}, MT / 4);
-#else
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        const int col = 16 * mt + 4 * q;
-        const f32x4 rv0 = T0.arg[mt] * scl0;               // :503
-        const f32x4 rv1 = T1.arg[mt] * scl1;
-#if !(HMX_RABL & 2)
-        if (live0 && col < Kp) st4(row0 + col, rv0);
-        if (live1 && col < Kp) st4(row1 + col, rv1);
-#endif
-#if !(HMX_RABL & 1)
-        if (joint) {
-            const f32x4 sm = rv0 + rv1;
-            f32x4 ss;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) ss[r] = row16_sum(sm[r]);      // (:506-507)
-            if (c16 == 0) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) atomicAdd(sd0 + col + r, (double)ss[r]);
-            }
-        } else {
-            f32x4 s0, s1;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                s0[r] = row16_sum(rv0[r]);
-                s1[r] = row16_sum(rv1[r]);
-            }
-            if (c16 == 0) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    atomicAdd(sd0 + col + r, (double)s0[r]);
-                    if (has1) atomicAdd(sd1 + col + r, (double)s1[r]);
-                }
-            }
-        }
-#endif
-    }
-#endif
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1512,8 +1420,8 @@ __global__ __launch_bounds__(64 * WIDE3_WAVES, 1) void k_assign_wide3(AssignArgs
     }
     if (has0) {
         float scl0, scl1 = 0.f;
-        round_post_pass1<MT, true, true, false, (HMX_ROUND_PK != 0 && MT <= 8)>(sig, rpL, lrpL, q, T0, scl0, km_acc, ent_acc);
-        if (has1) round_post_pass1<MT, true, true, false, (HMX_ROUND_PK != 0 && MT <= 8)>(sig, rpL, lrpL, q, T1, scl1, km_acc, ent_acc);
+        round_post_pass1<MT, true, true, false, (MT <= 8)>(sig, rpL, lrpL, q, T0, scl0, km_acc, ent_acc);
+        if (has1) round_post_pass1<MT, true, true, false, (MT <= 8)>(sig, rpL, lrpL, q, T1, scl1, km_acc, ent_acc);
         W3STAMP(5);
         round_post_pass2<MT>(a.R, a.Kp, Sd, c16, q, T0, scl0, has1, T1, scl1);
     } else {
@@ -1900,8 +1808,8 @@ __global__ __launch_bounds__(64 * WIDE3_WAVES, 1) void k_sweep_wide3(AssignArgs 
             }
             if (has0) {
                 float scl0, scl1 = 0.f;
-                round_post_pass1<MT, true, true, false, (HMX_ROUND_PK != 0 && MT <= 6)>(sig, rpL, lrpL, q, T0, scl0, km_acc, ent_acc);
-                if (has1) round_post_pass1<MT, true, true, false, (HMX_ROUND_PK != 0 && MT <= 6)>(sig, rpL, lrpL, q, T1, scl1, km_acc, ent_acc);
+                round_post_pass1<MT, true, true, false, (MT <= 6)>(sig, rpL, lrpL, q, T0, scl0, km_acc, ent_acc);
+                if (has1) round_post_pass1<MT, true, true, false, (MT <= 6)>(sig, rpL, lrpL, q, T1, scl1, km_acc, ent_acc);
                 round_post_pass2<MT>(a.R, a.Kp, Sd, c16, q, T0, scl0, has1, T1, scl1);
             }
             SWSEG(8);                                                    // 8: finishing passes
@@ -2032,7 +1940,7 @@ static inline void wide3_prof_dump(int, hipStream_t) {}
 static inline void sweep3_prof_dump(int, int, hipStream_t) {}
 #endif
 
-template <int MT, int KS, bool BF3T>
+template <int MT, int KS, bool BF3>   // BF3: distance GEMM on the bf16 pipe (round_compute_bf3)
 __global__ __launch_bounds__(ROUND_THREADS) void k_round(RoundArgs a) {
     if (a.frozen && *a.frozen) return;   // an earlier sweep of this cluster() call timed out: R, O, the objective block stay as it left them
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -2055,8 +1963,6 @@ __global__ __launch_bounds__(ROUND_THREADS) void k_round(RoundArgs a) {
     const int GKg = a.G * K16;                         // entries of the global tables O_start, S_old, O_out
     const int GKs = (a.G + 1) * K16;                   // stride of a slot table / of a rank's share of a peer box (row G: cluster mass, group-affine map only)
     const int LDY = a.ldy_lds;
-    constexpr bool LOG2 = HMX_ROUND_EXP2 != 0, A2TAB = HMX_ROUND_A2TAB != 0;
-    constexpr bool BF3 = BF3T && LOG2;                                   // distance GEMM on the bf16 pipe (round_compute_bf3)
     float* Ys0 = reinterpret_cast<float*>(smem);                         // K16 x LDY, or the three bf16 planes of the centroids
     unsigned* Yb0 = reinterpret_cast<unsigned*>(smem);
     // landing zones of the waves' Z_cos rows (global -> LDS directly): waves x ROUND_TPW tiles x 16 rows x dp floats,
@@ -2110,11 +2016,7 @@ __global__ __launch_bounds__(ROUND_THREADS) void k_round(RoundArgs a) {
                 double v = 0.0;
 #pragma unroll
                 for (int s = 0; s < HMX_ROUND_SLOTS; ++s) v += ld_agent(sn + (size_t)s * GKs);
-#if HMX_ROUND_RETURNING
-                for (int r = 0; r < a.n_ranks; ++r) xchg_sys(a.peer_box[r] + box_data(a.n_ranks, GKs, b & 1, a.rank) + i, v);
-#else
-                for (int r = 0; r < a.n_ranks; ++r) st_sys(a.peer_box[r] + box_data(a.n_ranks, GKs, b & 1, a.rank) + i, v);
-#endif
+                for (int r = 0; r < a.n_ranks; ++r) xchg_sys(a.peer_box[r] + box_data(a.n_ranks, GKs, b & 1, a.rank) + i, v);   // returning: see k_round's slot adds
             }
             WAIT_VMEM_ALL();
             __syncthreads();
@@ -2153,8 +2055,7 @@ __global__ __launch_bounds__(ROUND_THREADS) void k_round(RoundArgs a) {
     for (int i = tid; i < K16; i += ROUND_THREADS) {
         const float sgm = (i < a.K) ? a.sigma[i] : 0.f;
         sig[i] = sgm;
-        if (LOG2) nis[i] = (i < a.K) ? -(TWO_LOG2E / sgm) : -200.f;   // the accumulators start here; pads: Y row 0 -> 2^-200 == 0
-        else nis[i] = (i < a.K) ? -1.0f / sgm : -60.f;               // pads: Y row 0 -> dist 2 -> arg -120 -> exp == 0
+        nis[i] = (i < a.K) ? -(TWO_LOG2E / sgm) : -200.f;   // the accumulators start here; pads: Y row 0 -> 2^-200 == 0
     }
     for (int i = tid; i < GK; i += ROUND_THREADS) {
         Ocur[i] = a.O_start[(ga ? g_own * K16 : 0) + i];
@@ -2184,7 +2085,7 @@ __global__ __launch_bounds__(ROUND_THREADS) void k_round(RoundArgs a) {
     for (int i = tid; i < K16 * KS; i += ROUND_THREADS) {
         const int row = i / KS, c4 = i - row * KS;
         f32x4 y = ld4(a.Y + (size_t)row * a.ldy + 4 * c4);
-        if (LOG2) y *= (row < a.K) ? TWO_LOG2E / a.sigma[row] : 0.f;   // rows scaled by c_k: the products are exp2 arguments
+        y *= (row < a.K) ? TWO_LOG2E / a.sigma[row] : 0.f;   // rows scaled by c_k: the products are exp2 arguments
         st4(Ys0 + (size_t)row * LDY + 4 * c4, y);
     }
     __syncthreads();
@@ -2198,7 +2099,7 @@ __global__ __launch_bounds__(ROUND_THREADS) void k_round(RoundArgs a) {
     // configs[1] (G K16 = 128) 129.5-131.8 -> 126.7 us per sweep, but C3 (896 entries: 14 adds per lane from ONE wave, behind
     // the other waves' row stores in the CU's memory pipeline) 322 -> 390 us -- there everybody publishes as before.
     bool pubwave = false;
-    if (HMX_ROUND_PUBWAVE && GK <= 256 && !ga) {
+    if (GK <= 256 && !ga) {
         int max_ntl = 0;
         for (int bb = 0; bb < a.nblk; ++bb) max_ntl = max(max_ntl, bsN[bb]);
         pubwave = ROUND_TPW * (blockIdx.x + (multi ? (int)gridDim.x - 1 : (int)gridDim.x) * (ROUND_WAVES - 1)) >= max_ntl;
@@ -2345,11 +2246,11 @@ __global__ __launch_bounds__(ROUND_THREADS) void k_round(RoundArgs a) {
             if (late) request();
             return;
         }
-        round_compute<MT, KS, LOG2>(Ys, nis, LDY, c16, q, Zf[0], T[0]);
+        round_compute<MT, KS>(Ys, nis, LDY, c16, q, Zf[0], T[0]);
         __builtin_amdgcn_sched_barrier(0);
         if (second && !late) request();
         __builtin_amdgcn_sched_barrier(0);
-        round_compute<MT, KS, LOG2>(Ys, nis, LDY, c16, q, Zf[1], T[1]);
+        round_compute<MT, KS>(Ys, nis, LDY, c16, q, Zf[1], T[1]);
         __builtin_amdgcn_sched_barrier(0);
         if (late) request();
     };
@@ -2384,11 +2285,10 @@ __global__ __launch_bounds__(ROUND_THREADS) void k_round(RoundArgs a) {
     // The sums all workgroups added for block bp, per own entry: own group's row so[n], cluster-mass row st[n].  Polls until
     // every entry's count fields (bits 55.. of the four slot words) add up to the number of contributors -- ng workgroups of
     // the own group, all nwg for the cluster masses; the words that pass the test ARE the data (2^-32 fixed point).
-#ifndef HMX_GA_SLOTS
 #define HMX_GA_SLOTS 2   /* slot tables the group-affine map spreads a block's adds over AT MOST (of the HMX_ROUND_SLOTS allocated; a.ga_slots of them are
                             used): every slot is two more loads per entry of the poll; 8 / 4 / 2 / 1 measured (profiles/r06_ab_k_round_slots_poll.txt):
                             contention on the words only costs on large grids (one slot: C3 294 vs 242 us, configs[1] 110.5 vs 112 us) */
-#endif
+#define HMX_GA_POLL_SLEEP 2   /* s_sleep units (64 clocks each) between two polls of ga_fetch (8 measured in the same file: no faster) */
     static_assert(HMX_GA_SLOTS <= HMX_ROUND_SLOTS, "the slot tables are allocated for HMX_ROUND_SLOTS");
     constexpr unsigned long long FX_MASK = (1ull << 55) - 1ull;
     auto ga_fetch = [&](int bp, double (&so)[2], double (&st)[2]) {
@@ -2420,9 +2320,6 @@ __global__ __launch_bounds__(ROUND_THREADS) void k_round(RoundArgs a) {
                 ok = ok && co == (unsigned)ng && ct == (unsigned)nwg;
             }
             if (__all(ok) || failed) break;
-#ifndef HMX_GA_POLL_SLEEP
-#define HMX_GA_POLL_SLEEP 2
-#endif
             __builtin_amdgcn_s_sleep(HMX_GA_POLL_SLEEP);
             if (++spins > a.spin_limit) { failed = true; break; }   // (a wait that gave up is not repeated block after block: the launch is lost)
         }
@@ -2487,13 +2384,13 @@ __global__ __launch_bounds__(ROUND_THREADS) void k_round(RoundArgs a) {
             if (k < K16) {
                 const double v = Sd[k];
                 Sd[k] = 0.0;
-                if (A2TAB) a2s += v * (double)(lrpT[k] * sig[k]);       // (:402), see round_post_pass1
+                a2s += v * (double)(lrpT[k] * sig[k]);       // (:402), see round_post_pass1
                 const unsigned long long w = (1ull << 55) + (unsigned long long)__double2ll_rn(v * 4294967296.0);
                 __hip_atomic_fetch_add(dst + (size_t)g_own * K16 + k, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __hip_atomic_fetch_add(dst + (size_t)a.G * K16 + k, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
-        if (A2TAB) ent_acc += a2s;
+        ent_acc += a2s;
     };
 
     if (!service) {
@@ -2538,7 +2435,7 @@ __global__ __launch_bounds__(ROUND_THREADS) void k_round(RoundArgs a) {
 #pragma unroll
                 for (int s = 0; s < 8; ++s) add[n][s] = 0.0;
                 so[n] = a.S_old[(size_t)b * GKg + i];
-                if (b > 0 && !(HMX_RABL & 8)) {
+                if (b > 0) {
                     if (!multi) {
                         const double* sn = a.S_new + (size_t)(b - 1) * HMX_ROUND_SLOTS * GKs + i;
 #pragma unroll
@@ -2618,11 +2515,11 @@ __global__ __launch_bounds__(ROUND_THREADS) void k_round(RoundArgs a) {
         if (j_first < ntl) {
             float scl0, scl1 = 0.f;
             const bool has1 = j_first + 1 < ntl;
-            round_post_pass1<MT, true, LOG2, A2TAB>(sig, rpT, lrpT, q, T[0], scl0, km_acc, ent_acc);
+            round_post_pass1<MT, true, true, true>(sig, rpT, lrpT, q, T[0], scl0, km_acc, ent_acc);
             __builtin_amdgcn_sched_barrier(0);
             round_store_rows<MT>(a.R, a.Kp, q, T[0], scl0);
             __builtin_amdgcn_sched_barrier(0);
-            if (has1) round_post_pass1<MT, true, LOG2, A2TAB>(sig, rpT, lrpT, q, T[1], scl1, km_acc, ent_acc);
+            if (has1) round_post_pass1<MT, true, true, true>(sig, rpT, lrpT, q, T[1], scl1, km_acc, ent_acc);
             __builtin_amdgcn_sched_barrier(0);
             round_post_pass2<MT, false>(a.R, a.Kp, Sd, c16, q, T[0], scl0, has1, T[1], scl1);
         }
@@ -2642,10 +2539,10 @@ __global__ __launch_bounds__(ROUND_THREADS) void k_round(RoundArgs a) {
                 } else {
                     RoundZ<KS> XZ;
                     round_issue_z<KS>(a.Zcos, X.cell, q, XZ);
-                    round_compute<MT, KS, LOG2>(Ys, nis, LDY, c16, q, XZ, X);
+                    round_compute<MT, KS>(Ys, nis, LDY, c16, q, XZ, X);
                 }
                 float sclx;
-                round_post_pass1<MT, true, LOG2, A2TAB>(sig, rpT, lrpT, q, X, sclx, km_acc, ent_acc);
+                round_post_pass1<MT, true, true, true>(sig, rpT, lrpT, q, X, sclx, km_acc, ent_acc);
                 round_post_pass2<MT>(a.R, a.Kp, Sd, c16, q, X, sclx, false, X, 0.f);
             }
         }
@@ -2668,11 +2565,11 @@ __global__ __launch_bounds__(ROUND_THREADS) void k_round(RoundArgs a) {
                     olds[t] = 0.0;
                     if (i < GK) {
                         const double v = Sd[i];
-                        if (A2TAB) a2s += v * (double)(lrpT[i] * sig[i % K16]);   // (:402), see round_post_pass1
+                        a2s += v * (double)(lrpT[i] * sig[i % K16]);   // (:402), see round_post_pass1
                         if (v != 0.0) olds[t] = atomicAdd(dst + i, v);
                     }
                 }
-                if (A2TAB) ent_acc += a2s;
+                ent_acc += a2s;
                 WAIT_VMEM_ALL();
 #pragma unroll
                 for (int t = 0; t < 4; ++t) asm volatile("" ::"v"(olds[t]));
@@ -2686,14 +2583,10 @@ __global__ __launch_bounds__(ROUND_THREADS) void k_round(RoundArgs a) {
             double a2s = 0.0;
             for (int i = tid; i < GK; i += ROUND_THREADS) {
                 double v = Sd[i];
-                if (A2TAB) a2s += v * (double)(lrpT[i] * sig[i % K16]);   // sum over this block's cells of R sigma log(ratio^theta) (:402), see round_post_pass1
-#if HMX_ROUND_RETURNING
+                a2s += v * (double)(lrpT[i] * sig[i % K16]);   // sum over this block's cells of R sigma log(ratio^theta) (:402), see round_post_pass1
                 if (v != 0.0) { const double old = atomicAdd(dst + i, v); asm volatile("" ::"v"(old)); }
-#else
-                if (v != 0.0) atomicAdd(dst + i, v);
-#endif
             }
-            if (A2TAB) ent_acc += a2s;
+            ent_acc += a2s;
         }
         WAIT_VMEM_ALL();   // the sums are performed (and the next operands landed)
         wg_barrier_lds();
@@ -4918,11 +4811,7 @@ __global__ __launch_bounds__(256) void k_peer_selftest(double* const* peer_box, 
         const unsigned long long tk = token * 65536ull + (unsigned long long)it;
         const int par = it & 1;
         for (int r = 0; r < n_ranks; ++r)
-#if HMX_ROUND_RETURNING
             for (int i = tid; i < npay; i += 256) xchg_sys(peer_box[r] + box_data(n_ranks, GK, par, rank) + i, (double)(tk % 1000003ull) + i);
-#else
-            for (int i = tid; i < npay; i += 256) st_sys(peer_box[r] + box_data(n_ranks, GK, par, rank) + i, (double)(tk % 1000003ull) + i);
-#endif
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (tid < n_ranks) st_sys(reinterpret_cast<unsigned long long*>(peer_box[tid]) + tok0 + rank, tk);
@@ -4984,7 +4873,7 @@ static void launch_round_ks(const RoundArgs& a, int mt, int wgs, size_t sm, hipS
 // extra-tile loop, one tile per wave at a time, where the split is not hidden -- all 10 M cells of configs[3] on one GPU:
 // 3.22 ms per sweep against 3.03, profiles/r04_ab_k_round_bf16_pipe.txt) -- and for engines created under HMX_ROUND_F32=1 (`allow_bf16` false), the switch of the A/B runs and of the direct A/B test.
 bool round_uses_bf16_pipe(int K16, int dp, int G, int B, int V, bool extra_tiles, bool allow_bf16, bool ga, int nblk) {
-    return HMX_ROUND_BF3 && HMX_ROUND_EXP2 && allow_bf16 && !extra_tiles && round_lds_bytes(K16, dp, G, B, V, true, ga, nblk) <= HMX_ROUND_LDS_LIMIT;
+    return allow_bf16 && !extra_tiles && round_lds_bytes(K16, dp, G, B, V, true, ga, nblk) <= HMX_ROUND_LDS_LIMIT;
 }
 
 int launch_round(const RoundArgs& a_in, int mt, int wgs, hipStream_t s, bool extra_tiles, bool allow_bf16) {

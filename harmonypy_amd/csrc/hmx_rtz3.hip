@@ -34,22 +34,14 @@
 #include "hmx_internal.h"
 #include "hmx_device.h"
 
-#ifndef HMX_RTZ3_Z_NT
-#define HMX_RTZ3_Z_NT 1  /* k_rtz3c: Z rows requested non-temporal like the R rows (0: experiment of round 6 -- Z_cos, 200 MB at C3, read by both
-                            kernels of a round, left cacheable so that it might stay in the 256 MB memory-side cache: profiles/r06_ab_zcos_cacheable.txt) */
-#endif
-#ifndef HMX_RTZ3_NT
-#define HMX_RTZ3_NT 1    /* the rows are read once per pass: non-temporal requests (micro-benchmark of this very pattern: 6.2 -> 6.9 TB/s) */
-#endif
-// (defined in FRONT of dma16: behind it -- where it stood until round 4 -- `#if HMX_RTZ3_NT` read an undefined macro, i.e. 0, and
-// every request of the streaming kernels went out without the hint)
 namespace {
 
 // one 1 KB piece global -> LDS: lane l brings the 16 bytes at `base` + `voff` (= 16 l) to LDS byte address `zone` + 16 l.
 // `base` is wave-uniform and travels in scalar registers (the SADDR form of the instruction): the stream's addresses cost
 // no vector registers, however far ahead the compiler forms them.  Inline assembly on purpose: the
-// builtin makes the compiler drain vmcnt before any later LDS read.
-template <bool NT = true>
+// builtin makes the compiler drain vmcnt before any later LDS read.  Every request is non-temporal: the rows are read once
+// per pass (micro-benchmark of this very pattern: 6.2 -> 6.9 TB/s), the Z rows of k_rtz3c included (leaving Z_cos, 200 MB at
+// C3 and read by both kernels of a round, cacheable for the 256 MB memory-side cache lost: profiles/r06_ab_zcos_cacheable.txt).
 __device__ __forceinline__ void dma16(const void* base_, unsigned voff, unsigned zone_) {
     const unsigned zone = __builtin_amdgcn_readfirstlane(zone_);   // (likewise: under pressure a uniform LDS address may sit in a vector register)
     // (under register pressure the compiler may park a wave-uniform pointer in vector registers: say it again that it is
@@ -58,11 +50,7 @@ __device__ __forceinline__ void dma16(const void* base_, unsigned voff, unsigned
     const unsigned long long bits = (unsigned long long)base_;
     const void* base = (const void*)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(bits >> 32)) << 32) |
                                      (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)bits));
-#if HMX_RTZ3_NT
-    if (NT) asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 nt" ::"v"(voff), "s"(base), "s"(zone) : "memory", "m0");
-    else
-#endif
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "s"(zone) : "memory", "m0");
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 nt" ::"v"(voff), "s"(base), "s"(zone) : "memory", "m0");
 }
 __device__ __forceinline__ unsigned lds_addr(const void* p) {
     return __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) const void*)p);
@@ -77,9 +65,6 @@ __device__ __forceinline__ void wait_vmcnt() {   // gfx9 encoding: vmcnt[3:0] | 
 }  // namespace
 
 #define RTZ3_WAVES 4
-#ifndef HMX_RTZ3_ABL
-#define HMX_RTZ3_ABL 0   /* timing experiments only (results become wrong): 1 no MFMAs (the stream alone), 2 no requests after the prologue (the arithmetic alone) */
-#endif
 
 #ifdef HMX_RTZ3_PROF   /* timing experiments only: s_memtime stamps per wave */
 #define R3STAMP(k) do { if (lane == 0 && a.prof) a.prof[((size_t)blockIdx.x * RTZ3_WAVES + wv) * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
@@ -236,7 +221,7 @@ __global__ __launch_bounds__(64 * RTZ3_WAVES, 2) void k_rtz3(Rtz3Args a) {
         float* Zt = Rt + 16 * Kp;
         bw = bw_next;
         const bool next = i + 1 < n_mine;                           // wave-uniform
-        const bool more = i + 2 < n_mine && !(HMX_RTZ3_ABL & 2);
+        const bool more = i + 2 < n_mine;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             const int set = ks & 1;
@@ -251,11 +236,7 @@ __global__ __launch_bounds__(64 * RTZ3_WAVES, 2) void k_rtz3(Rtz3Args a) {
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) {
-#if HMX_RTZ3_ABL & 1
-                    acc[mt][nt][0] += afr[set][mt] * bfr[nt];
-#else
                     acc[mt][nt] = MFMA16(afr[set][mt], bfr[nt], acc[mt][nt]);
-#endif
                     if (ks == 3) {
                         const int m = mt * NT + nt + 1;             // MFMAs of this k-step issued so far
                         if (m % GAP == 0 && m / GAP - 1 < NI && m < OPEN) {
@@ -285,11 +266,7 @@ __global__ __launch_bounds__(64 * RTZ3_WAVES, 2) void k_rtz3(Rtz3Args a) {
     // of the SIMD covers the read phase when it can.
     for (int i = 0; i < n_mine; ++i) {
         asm volatile("" ::: "memory");
-#if HMX_RTZ3_ABL & 2
-        wait_vmcnt<0>();
-#else
         if (i + 1 < n_mine) wait_vmcnt<NI>(); else wait_vmcnt<0>();
-#endif
         asm volatile("" ::: "memory");
         const int c0 = c_mine + 16 * stride * i;
         float* Rt = lds + (size_t)(2 * wv + (i & 1)) * buf_floats;
@@ -316,7 +293,7 @@ __global__ __launch_bounds__(64 * RTZ3_WAVES, 2) void k_rtz3(Rtz3Args a) {
             zfr[ks] = ld4(Zt + (size_t)(4 * q + ks) * DP + 4 * min(c16, KS - 1));
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // the buffer is in registers: it may be overwritten
-        if (i + 2 < n_mine && !(HMX_RTZ3_ABL & 2)) {
+        if (i + 2 < n_mine) {
 #pragma unroll
             for (int p = 0; p < NI; ++p) issue_piece(i & 1, p);
             advance();
@@ -429,7 +406,7 @@ __global__ __launch_bounds__(64 * RTZ3C_WAVES, 1) void k_rtz3c(Rtz3Args a) {
             if (p + 1 < NR || 1024 * p + lane16 < 64 * Kp) dma16(r + 1024 * p, lane16, zb + 1024u * p);
 #pragma unroll
         for (int it = 0; it < NZ; ++it)
-            if (1024 * (it + 1) <= 64 * DP || 1024 * it + lane16 < 64 * DP) dma16<(HMX_RTZ3_Z_NT != 0)>(z + 1024 * it, lane16, zb + r_bytes + 1024u * it);
+            if (1024 * (it + 1) <= 64 * DP || 1024 * it + lane16 < 64 * DP) dma16(z + 1024 * it, lane16, zb + r_bytes + 1024u * it);
         if (lane == 0) dma16(id, lane16, zb + r_bytes + 64u * DP);
     };
     auto request_pair = [&](int i) {                                // (a missing second tile: the first one again, never read)

@@ -5,6 +5,7 @@ reloaded behind `s_waitcnt vmcnt(0)` (drains every load in flight), a pointer th
 reads into flat loads (which also count on vmcnt).
 
     python scripts/kernel_audit.py [libhmx.so] [name filter]
+    python scripts/kernel_audit.py --compare a/libhmx.so b/libhmx.so     device code of two builds, instruction by instruction
 
 Needs only the LLVM tools of the ROCm image (no GPU).  `audit()` is what tests/test_kernel_audit.py calls."""
 import os
@@ -229,9 +230,59 @@ def audit(lib=None, name_filter=""):
     return [dict(name=n, demangled=dm[n], **meta[n], **ins.get(n, {})) for n in sorted(pick, key=lambda x: dm[x])]
 
 
+def _kernel_streams(lib):
+    """{mangled name: (metadata, [instruction lines without addresses and // comments])} over all code objects of the library"""
+    res = {}
+    with tempfile.TemporaryDirectory() as wd:
+        for co in extract_code_objects(lib, wd):
+            meta = kernel_metadata(co)
+            dis = _run(os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", co)
+            for m in re.finditer(r"^[0-9a-f]+ <([^>]+)>:\n(.*?)(?=^[0-9a-f]+ <|\Z)", dis, re.M | re.S):
+                if m.group(1) in meta:
+                    lines = [" ".join(l.split("//")[0].split()) for l in m.group(2).split("\n")]
+                    res[m.group(1)] = (meta[m.group(1)], [l for l in lines if l])
+    return res
+
+
+def compare(lib_a, lib_b, out=sys.stdout):
+    """Device code of two builds, kernel by kernel: metadata and instruction stream.  Prints the kernels present on one side
+    only and the kernels that differ (with the opcodes of their differing lines); returns the number of both."""
+    def stamp(lib):
+        try:
+            return open(lib + ".buildid").read().strip()
+        except OSError:
+            return "?"
+    A, B = _kernel_streams(lib_a), _kernel_streams(lib_b)
+    print(f"a: {lib_a} (build {stamp(lib_a)}), {len(A)} kernels\nb: {lib_b} (build {stamp(lib_b)}), {len(B)} kernels", file=out)
+    print(_run(os.path.join(LLVM, "clang"), "--version").split("\n")[0], file=out)
+    dm = demangle(sorted(set(A) | set(B)))
+    only = sorted(set(A) ^ set(B))
+    for n in only:
+        print(f"only in {'a' if n in A else 'b'}: {dm[n]}", file=out)
+    differ = 0
+    for n in sorted(set(A) & set(B), key=lambda x: dm[x]):
+        (ma, ia), (mb, ib) = A[n], B[n]
+        if ma == mb and ia == ib:
+            continue
+        differ += 1
+        lines = [(x, y) for x, y in zip(ia, ib) if x != y]
+        ops = sorted({x.split()[0] for x, _ in lines} | {y.split()[0] for _, y in lines})
+        # lines that are the same but for their last operand, an immediate: the change of that immediate (else "other")
+        imm = [(x.rsplit(", ", 1), y.rsplit(", ", 1)) for x, y in lines]
+        moved = sorted({str(int(q[1], 0) - int(p[1], 0)) if p[0] == q[0] and all(re.fullmatch(r"(0x)?[0-9a-f]+", v[-1]) for v in (p, q)) else "other"
+                        for p, q in imm})
+        print(f"differs: {dm[n]}: instructions {len(ia)} -> {len(ib)}, metadata {'same' if ma == mb else f'{ma} -> {mb}'}, "
+              f"{len(lines)} differing lines, opcodes {ops}, immediates moved by {moved}", file=out)
+    print(f"{len(set(A) & set(B)) - differ} kernels identical, {differ} differ, {len(only)} on one side only", file=out)
+    return differ + len(only)
+
+
 if __name__ == "__main__":
     if not tools_available():
         sys.exit(f"LLVM tools not found under {LLVM}")
+    if "--compare" in sys.argv:   # kernel_audit.py --compare a.so b.so
+        i = sys.argv.index("--compare")
+        sys.exit(1 if compare(sys.argv[i + 1], sys.argv[i + 2]) else 0)
     lib = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1].endswith(".so") else None
     flt = sys.argv[-1] if len(sys.argv) > 1 and not sys.argv[-1].endswith(".so") and sys.argv[-1] != "--inflight" else ""
     if "--inflight" in sys.argv:
