@@ -26,7 +26,7 @@ OBJ_DIR = os.path.join(ROOT, "build", "obj")
 SOURCES = ["hmx_kernels.hip", "hmx_rtz3.hip", "hmx_lisi.hip", "hmx_io.hip", "hmx_score.hip", "hmx_capi.cpp"]
 PUBLIC_HEADERS = [os.path.join(ROOT, "include", "hmx.h"), os.path.join(ROOT, "include", "hmx_device_io.h"),
                   os.path.join(ROOT, "include", "hmx_map.h"), os.path.join(ROOT, "include", "hmx_knn.h"),
-                  os.path.join(ROOT, "include", "hmx_score.h")]
+                  os.path.join(ROOT, "include", "hmx_score.h"), os.path.join(ROOT, "include", "hmx_census.h")]
 HEADERS = [os.path.join(CSRC, "hmx_internal.h"), os.path.join(CSRC, "hmx_device.h"),
            os.path.join(CSRC, "hmx_score_kernels.h")] + PUBLIC_HEADERS
 BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function"]

@@ -1,4 +1,4 @@
-"""ctypes binding of libhmx.so (include/hmx.h, include/hmx_device_io.h, include/hmx_map.h, include/hmx_knn.h, include/hmx_score.h).  Thin: argument marshalling and error text only.
+"""ctypes binding of libhmx.so (include/hmx.h, include/hmx_device_io.h, include/hmx_map.h, include/hmx_knn.h, include/hmx_score.h, include/hmx_census.h).  Thin: argument marshalling and error text only.
 
 The library is the product's compute path; there is no fallback.  Importing this module
 without a built ``libhmx.so`` raises, and every entry point raises ``HmxError`` with the
@@ -37,6 +37,8 @@ MAP_EXPORTS = ["hmx_reference_summary", "hmx_map_query"]
 KNN_EXPORTS = ["hmx_knn_predict", "hmx_knn_slices"]
 # include/hmx_score.h: cluster moments and the per-cell mapping score (same ABI version; its own header)
 SCORE_EXPORTS = ["hmx_cluster_moments", "hmx_mapping_score"]
+# include/hmx_census.h: the launch census (test instrumentation; same ABI version; its own header)
+CENSUS_EXPORTS = ["hmx_launch_census_enable", "hmx_launch_census"]
 HMX_PEER_HANDLE_BYTES = 64
 HMX_ABI_VERSION = 8
 HMX_UNIQUE_ID_BYTES = 128
@@ -121,7 +123,9 @@ def load():
     lib.hmx_knn_slices.argtypes = [i32, i64, i64, i32, i32]
     lib.hmx_cluster_moments.argtypes = [vp, C.c_int, vp, i32, vp, vp, vp, vp]
     lib.hmx_mapping_score.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
-    for name in EXPORTS + DEVICE_IO_EXPORTS + MAP_EXPORTS + KNN_EXPORTS + SCORE_EXPORTS:
+    lib.hmx_launch_census_enable.argtypes = [C.c_int]
+    lib.hmx_launch_census.argtypes = [C.c_char_p, C.c_size_t]
+    for name in EXPORTS + DEVICE_IO_EXPORTS + MAP_EXPORTS + KNN_EXPORTS + SCORE_EXPORTS + CENSUS_EXPORTS:
         if name not in ("hmx_last_error", "hmx_destroy", "hmx_build_id"):
             getattr(lib, name).restype = C.c_int
     lib.hmx_build_id.restype = C.c_char_p
@@ -132,6 +136,18 @@ def load():
 def build_id() -> str:
     """Identity of the kernel set in the loaded library (hash of csrc/ and hmx.h taken at build time)."""
     return load().hmx_build_id().decode()
+
+
+def launch_census(on=None):
+    """The launch census of include/hmx_census.h (test instrumentation).  ``on`` True: clear the set and start noting
+    kernel launches; False: stop.  Returns the symbol names of the kernels launched since it was last enabled."""
+    lib = load()
+    if on is not None:
+        lib.hmx_launch_census_enable(1 if on else 0)
+    n = lib.hmx_launch_census(None, 0)
+    buf = C.create_string_buffer(max(n, 1))
+    lib.hmx_launch_census(buf, n)
+    return [s for s in buf.value.decode().split("\n") if s]
 
 
 def _check(rc):

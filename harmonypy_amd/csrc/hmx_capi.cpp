@@ -11,10 +11,13 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <mutex>
+#include <set>
 #include <string>
 #include <vector>
 
 #include "hmx.h"
+#include "hmx_census.h"
 #include "hmx_device_io.h"
 #include "hmx_knn.h"
 #include "hmx_map.h"
@@ -24,6 +27,15 @@
 #ifdef RTZ_PROF
 void rtz_prof_dump();
 #endif
+
+// ---- launch census (include/hmx_census.h): the kernel handles HMX_LAUNCH saw while it was on
+bool g_hmx_census_on = false;
+static std::mutex g_census_mu;
+static std::set<const void*> g_census;
+void hmx_census_note(const void* kernel) {
+    std::lock_guard<std::mutex> lk(g_census_mu);
+    g_census.insert(kernel);
+}
 
 struct hmx_nccl_id { char internal[HMX_UNIQUE_ID_BYTES]; };   // layout of ncclUniqueId (rccl.h)
 
@@ -425,6 +437,38 @@ extern "C" {
 
 const char* hmx_last_error(void) { return g_err.c_str(); }
 int hmx_abi_version(void) { return HMX_ABI_VERSION; }
+
+int hmx_launch_census_enable(int on) {
+    std::lock_guard<std::mutex> lk(g_census_mu);
+    if (on) g_census.clear();
+    g_hmx_census_on = on != 0;
+    return HMX_OK;
+}
+
+// A kernel's host handle is a data symbol of this library that carries the kernel's mangled name (the stub is
+// __device_stub__<name>), so dladdr names it without the runtime; hipKernelNameRefByPtr is asked where it does not.
+int hmx_launch_census(char* buf, size_t n) {
+    std::set<std::string> names;
+    {
+        std::lock_guard<std::mutex> lk(g_census_mu);
+        for (const void* k : g_census) {
+            Dl_info info{};
+            const char* nm = (dladdr(k, &info) && info.dli_sname && info.dli_saddr == k) ? info.dli_sname : nullptr;
+            if (!nm) nm = hipKernelNameRefByPtr(k, nullptr);
+            char hex[32];
+            if (!nm || !*nm) { snprintf(hex, sizeof hex, "?%p", k); nm = hex; }
+            names.insert(nm);
+        }
+    }
+    std::string all;
+    for (const std::string& s : names) { all += s; all += '\n'; }
+    if (buf && n > 0) {
+        const size_t c = std::min(n - 1, all.size());
+        std::memcpy(buf, all.data(), c);
+        buf[c] = 0;
+    }
+    return (int)(all.size() + 1);
+}
 
 int hmx_create(const hmx_config* cfg, hmx_engine** out) {
     if (!cfg || !out) return fail(HMX_ERR_ARG, "null argument");

@@ -9,6 +9,16 @@
 #define HMX_RTZ_NTW 4
 #define HMX_OBJ_SLOTS 64 /* objective partials are spread over this many fp64 slot pairs */
 
+// Launch census (include/hmx_census.h; test instrumentation): every launch of hmx_kernels.hip and hmx_rtz3.hip goes
+// through HMX_LAUNCH, which notes the kernel's host handle while the census is on -- off, one predictable branch.
+extern bool g_hmx_census_on;
+void hmx_census_note(const void* kernel);
+#define HMX_LAUNCH(kernel, grid, block, lds, stream, ...)                                                    \
+    do {                                                                                                    \
+        if (__builtin_expect(g_hmx_census_on, 0)) hmx_census_note(reinterpret_cast<const void*>(kernel));   \
+        hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);                                  \
+    } while (0)
+
 struct AssignArgs {
     const float* Zcos;     // N x dp
     const float* Y;        // K16 x ldy, unit rows, zero padded

@@ -4611,14 +4611,14 @@ static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 void launch_normalize_rows(const float* Z, float* Zc, int64_t N, int dp, hipStream_t s) {
     if (N <= 0) return;
-    hipLaunchKernelGGL(k_normalize_rows, dim3(cdiv(N, 16)), dim3(256), 0, s, Z, Zc, N, dp);
+    HMX_LAUNCH(k_normalize_rows, dim3(cdiv(N, 16)), dim3(256), 0, s, Z, Zc, N, dp);
 }
 
 void launch_y_normalize(const float* src, float* dst, int K, int K16, int d, int ldy, hipStream_t s) {
-    hipLaunchKernelGGL(k_y_normalize<float>, dim3(K16), dim3(64), 0, s, src, dst, K, d, ldy);
+    HMX_LAUNCH(k_y_normalize<float>, dim3(K16), dim3(64), 0, s, src, dst, K, d, ldy);
 }
 void launch_y_normalize_d(const double* src, float* dst, int K, int K16, int d, int ldy, hipStream_t s) {
-    hipLaunchKernelGGL(k_y_normalize<double>, dim3(K16), dim3(64), 0, s, src, dst, K, d, ldy);
+    HMX_LAUNCH(k_y_normalize<double>, dim3(K16), dim3(64), 0, s, src, dst, K, d, ldy);
 }
 
 int assign_grid(int ntiles, int nt_per_step, int max_wgs) {
@@ -4633,8 +4633,8 @@ static int lds_ldy(int dp) { return ((dp >> 2) & 1) ? dp : dp + 4; }  // (LDY/4)
 
 template <int MT>
 static void launch_assign_lds(const AssignArgs& a, bool penalty, int wgs, size_t sm, hipStream_t s) {
-    if (penalty) hipLaunchKernelGGL((k_assign_lds<MT, true>), dim3(wgs), dim3(64 * ASSIGN_WAVES), sm, s, a);
-    else hipLaunchKernelGGL((k_assign_lds<MT, false>), dim3(wgs), dim3(64 * ASSIGN_WAVES), sm, s, a);
+    if (penalty) HMX_LAUNCH((k_assign_lds<MT, true>), dim3(wgs), dim3(64 * ASSIGN_WAVES), sm, s, a);
+    else HMX_LAUNCH((k_assign_lds<MT, false>), dim3(wgs), dim3(64 * ASSIGN_WAVES), sm, s, a);
 }
 
 size_t assign_wide3_lds_bytes(int mt) {
@@ -4661,7 +4661,7 @@ int launch_sweep_wide3(const AssignArgs& a, int wgs, hipStream_t s) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_sweep_wide3<M>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
             attr_done = true;                                                                                         \
         }                                                                                                             \
-        hipLaunchKernelGGL((k_sweep_wide3<M>), dim3(wgs), dim3(64 * WIDE3_WAVES), sm, s, a);                           \
+        HMX_LAUNCH((k_sweep_wide3<M>), dim3(wgs), dim3(64 * WIDE3_WAVES), sm, s, a);                           \
         sweep3_prof_dump(wgs, a.nblk, s);                                                                             \
     } break;
     switch (a.mt) {
@@ -4720,7 +4720,7 @@ int launch_assign(const AssignArgs& a_in, bool penalty, int max_wgs, hipStream_t
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_assign_wide3<M>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
             attr_done = true;                                                                                         \
         }                                                                                                             \
-        hipLaunchKernelGGL((k_assign_wide3<M>), dim3(wgs3), dim3(64 * WIDE3_WAVES), sm3, s, a);                        \
+        HMX_LAUNCH((k_assign_wide3<M>), dim3(wgs3), dim3(64 * WIDE3_WAVES), sm3, s, a);                        \
         wide3_prof_dump(wgs3, s);                                                                                     \
     } break;
             if (sm3 <= 160 * 1024) {
@@ -4735,8 +4735,8 @@ int launch_assign(const AssignArgs& a_in, bool penalty, int max_wgs, hipStream_t
         const int wgs = std::max(1, std::min(2 * 256, cdiv(ntiles, WIDE_WAVES)));
 #define HMX_WIDE_CASE(M)                                                                                          \
     case M:                                                                                                       \
-        if (penalty) hipLaunchKernelGGL((k_assign_wide<M, true>), dim3(wgs), dim3(64 * WIDE_WAVES), sm, s, a);    \
-        else hipLaunchKernelGGL((k_assign_wide<M, false>), dim3(wgs), dim3(64 * WIDE_WAVES), sm, s, a);           \
+        if (penalty) HMX_LAUNCH((k_assign_wide<M, true>), dim3(wgs), dim3(64 * WIDE_WAVES), sm, s, a);    \
+        else HMX_LAUNCH((k_assign_wide<M, false>), dim3(wgs), dim3(64 * WIDE_WAVES), sm, s, a);           \
         break;
         switch (a.mt) {
             HMX_WIDE_CASE(1) HMX_WIDE_CASE(2) HMX_WIDE_CASE(3) HMX_WIDE_CASE(4) HMX_WIDE_CASE(5) HMX_WIDE_CASE(6) HMX_WIDE_CASE(7)
@@ -4748,18 +4748,18 @@ int launch_assign(const AssignArgs& a_in, bool penalty, int max_wgs, hipStream_t
     if (a.mt <= 7) {
         constexpr int NT = 2;
         const int wgs = assign_grid(ntiles, NT, max_wgs);
-        if (penalty) hipLaunchKernelGGL((k_assign<7, NT, true>), dim3(wgs), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((k_assign<7, NT, false>), dim3(wgs), dim3(256), 0, s, a);
+        if (penalty) HMX_LAUNCH((k_assign<7, NT, true>), dim3(wgs), dim3(256), 0, s, a);
+        else HMX_LAUNCH((k_assign<7, NT, false>), dim3(wgs), dim3(256), 0, s, a);
     } else if (a.mt <= 13) {
         constexpr int NT = 1;
         const int wgs = assign_grid(ntiles, NT, max_wgs);
-        if (penalty) hipLaunchKernelGGL((k_assign<13, NT, true>), dim3(wgs), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((k_assign<13, NT, false>), dim3(wgs), dim3(256), 0, s, a);
+        if (penalty) HMX_LAUNCH((k_assign<13, NT, true>), dim3(wgs), dim3(256), 0, s, a);
+        else HMX_LAUNCH((k_assign<13, NT, false>), dim3(wgs), dim3(256), 0, s, a);
     } else if (a.mt <= 20) {   // up to 320 clusters: the generic kernel's widest instance (51 KB of staged centroid columns)
         constexpr int NT = 1;
         const int wgs = assign_grid(ntiles, NT, max_wgs);
-        if (penalty) hipLaunchKernelGGL((k_assign<20, NT, true>), dim3(wgs), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((k_assign<20, NT, false>), dim3(wgs), dim3(256), 0, s, a);
+        if (penalty) HMX_LAUNCH((k_assign<20, NT, true>), dim3(wgs), dim3(256), 0, s, a);
+        else HMX_LAUNCH((k_assign<20, NT, false>), dim3(wgs), dim3(256), 0, s, a);
     } else {
         return -1;
     }
@@ -4839,7 +4839,7 @@ __global__ __launch_bounds__(256) void k_peer_selftest(double* const* peer_box, 
 
 void launch_peer_selftest(double* const* peer_box, double* my_box, int n_ranks, int rank, size_t GK, unsigned long long token, int iters,
                           unsigned* result, hipStream_t s) {
-    hipLaunchKernelGGL(k_peer_selftest, dim3(1), dim3(256), 0, s, peer_box, my_box, n_ranks, rank, GK, token, iters, result);
+    HMX_LAUNCH(k_peer_selftest, dim3(1), dim3(256), 0, s, peer_box, my_box, n_ranks, rank, GK, token, iters, result);
 }
 
 // k_round is compiled for Z_cos rows of 32, 52 and 64 floats (d <= 32, <= 52, <= 64: the engine pads
@@ -4853,7 +4853,7 @@ static void launch_round_t(const RoundArgs& a, int wgs, size_t sm, hipStream_t s
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_round<MT, KS, BF3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_done = true;
     }
-    hipLaunchKernelGGL((k_round<MT, KS, BF3>), dim3(wgs), dim3(ROUND_THREADS), sm, s, a);
+    HMX_LAUNCH((k_round<MT, KS, BF3>), dim3(wgs), dim3(ROUND_THREADS), sm, s, a);
 }
 template <int KS, bool BF3>
 static void launch_round_ks(const RoundArgs& a, int mt, int wgs, size_t sm, hipStream_t s) {
@@ -4900,13 +4900,13 @@ int rtz2_slab_floats(int mt, int dp) { return mt * (dp == 32 ? 2 : 4) * 256; }
 template <int NTD, bool ONES>
 static void launch_rtz2_n(RtzArgs& a, int mt, int wgs, size_t sm, hipStream_t s) {
     switch (mt) {
-        case 1: hipLaunchKernelGGL((k_rtz2<1, NTD, ONES>), dim3(wgs), dim3(256), sm, s, a); break;
-        case 2: hipLaunchKernelGGL((k_rtz2<2, NTD, ONES>), dim3(wgs), dim3(256), sm, s, a); break;
-        case 3: hipLaunchKernelGGL((k_rtz2<3, NTD, ONES>), dim3(wgs), dim3(256), sm, s, a); break;
-        case 4: hipLaunchKernelGGL((k_rtz2<4, NTD, ONES>), dim3(wgs), dim3(256), sm, s, a); break;
-        case 5: hipLaunchKernelGGL((k_rtz2<5, NTD, ONES>), dim3(wgs), dim3(256), sm, s, a); break;
-        case 6: hipLaunchKernelGGL((k_rtz2<6, NTD, ONES>), dim3(wgs), dim3(256), sm, s, a); break;
-        default: hipLaunchKernelGGL((k_rtz2<7, NTD, ONES>), dim3(wgs), dim3(256), sm, s, a); break;
+        case 1: HMX_LAUNCH((k_rtz2<1, NTD, ONES>), dim3(wgs), dim3(256), sm, s, a); break;
+        case 2: HMX_LAUNCH((k_rtz2<2, NTD, ONES>), dim3(wgs), dim3(256), sm, s, a); break;
+        case 3: HMX_LAUNCH((k_rtz2<3, NTD, ONES>), dim3(wgs), dim3(256), sm, s, a); break;
+        case 4: HMX_LAUNCH((k_rtz2<4, NTD, ONES>), dim3(wgs), dim3(256), sm, s, a); break;
+        case 5: HMX_LAUNCH((k_rtz2<5, NTD, ONES>), dim3(wgs), dim3(256), sm, s, a); break;
+        case 6: HMX_LAUNCH((k_rtz2<6, NTD, ONES>), dim3(wgs), dim3(256), sm, s, a); break;
+        default: HMX_LAUNCH((k_rtz2<7, NTD, ONES>), dim3(wgs), dim3(256), sm, s, a); break;
     }
 }
 
@@ -4938,7 +4938,7 @@ void launch_rtz2_reduce(const float* slab, int nslabs, int mt, int dp, int K16, 
                         hipStream_t s) {
     const int ntd = dp == 32 ? 2 : 4;
     const int seg_len = 8;   // slabs summed serially by one thread: short chains, the loads are latency-bound
-    hipLaunchKernelGGL(k_rtz2_reduce, dim3(cdiv(mt * ntd * 256, 256), cdiv(nslabs, seg_len)), dim3(256), 0, s, slab, nslabs, mt,
+    HMX_LAUNCH(k_rtz2_reduce, dim3(cdiv(mt * ntd * 256, 256), cdiv(nslabs, seg_len)), dim3(256), 0, s, slab, nslabs, mt,
                        ntd, K16, ld, out, task_grp, seg_len);
 }
 
@@ -4954,27 +4954,27 @@ int launch_kmeans_step(const float* Zcos, const float* C, const float* hn, const
     if (mt < 1 || mt > 7 || dp > 64) return -1;
     const size_t sm = ((size_t)K16 * a.ldy_lds + K16 + (size_t)K16 * a.ldc + K16 + (size_t)8 * 16 * KM_LDZ) * sizeof(float);
     switch (mt) {
-        case 1: hipLaunchKernelGGL((k_kmeans_step<1>), dim3(wgs), dim3(512), sm, s, a); break;
-        case 2: hipLaunchKernelGGL((k_kmeans_step<2>), dim3(wgs), dim3(512), sm, s, a); break;
-        case 3: hipLaunchKernelGGL((k_kmeans_step<3>), dim3(wgs), dim3(512), sm, s, a); break;
-        case 4: hipLaunchKernelGGL((k_kmeans_step<4>), dim3(wgs), dim3(512), sm, s, a); break;
-        case 5: hipLaunchKernelGGL((k_kmeans_step<5>), dim3(wgs), dim3(512), sm, s, a); break;
-        case 6: hipLaunchKernelGGL((k_kmeans_step<6>), dim3(wgs), dim3(512), sm, s, a); break;
-        default: hipLaunchKernelGGL((k_kmeans_step<7>), dim3(wgs), dim3(512), sm, s, a); break;
+        case 1: HMX_LAUNCH((k_kmeans_step<1>), dim3(wgs), dim3(512), sm, s, a); break;
+        case 2: HMX_LAUNCH((k_kmeans_step<2>), dim3(wgs), dim3(512), sm, s, a); break;
+        case 3: HMX_LAUNCH((k_kmeans_step<3>), dim3(wgs), dim3(512), sm, s, a); break;
+        case 4: HMX_LAUNCH((k_kmeans_step<4>), dim3(wgs), dim3(512), sm, s, a); break;
+        case 5: HMX_LAUNCH((k_kmeans_step<5>), dim3(wgs), dim3(512), sm, s, a); break;
+        case 6: HMX_LAUNCH((k_kmeans_step<6>), dim3(wgs), dim3(512), sm, s, a); break;
+        default: HMX_LAUNCH((k_kmeans_step<7>), dim3(wgs), dim3(512), sm, s, a); break;
     }
     return 0;
 }
 
 void launch_kmeans_sums(const float* slab, int wgs, int K16, int dp, int d, double* sums, hipStream_t s) {
-    hipLaunchKernelGGL(k_kmeans_sums, dim3(K16), dim3(256), 0, s, slab, wgs, K16, lds_ldy(dp), d, sums);
+    HMX_LAUNCH(k_kmeans_sums, dim3(K16), dim3(256), 0, s, slab, wgs, K16, lds_ldy(dp), d, sums);
 }
 
 void launch_kmeans_sums_from_stats(const double* Sr, const double* Oxr, int G, int K16, int ld, int d, double* sums, hipStream_t s) {
-    hipLaunchKernelGGL(k_kmeans_sums_from_stats, dim3(K16), dim3(256), 0, s, Sr, Oxr, G, K16, ld, d, sums);
+    HMX_LAUNCH(k_kmeans_sums_from_stats, dim3(K16), dim3(256), 0, s, Sr, Oxr, G, K16, ld, d, sums);
 }
 
 void launch_kmeans_update(const double* sums, float* C, float* hn, int K, int K16, int d, int ldy, hipStream_t s) {
-    hipLaunchKernelGGL(k_kmeans_update, dim3(K16), dim3(64), 0, s, sums, C, hn, K, d, ldy);
+    HMX_LAUNCH(k_kmeans_update, dim3(K16), dim3(64), 0, s, sums, C, hn, K, d, ldy);
 }
 
 bool rtz_wide_ok(int mt, int dp) { return mt >= 1 && mt <= 13 && dp % 16 == 0 && dp <= 208 && (mt > 7 || dp > 64); }
@@ -4988,19 +4988,19 @@ void launch_rtz_wide(const RtzArgs& a_in, int wgs, hipStream_t s) {
     a.ldz = ((16 * ntd + 31) / 32) * 32 + 16;
     const size_t sm = (size_t)2 * 16 * (a.ldr + a.ldz) * sizeof(float) + (256 + 256) * sizeof(int);
     switch (a.mt) {
-        case 1: hipLaunchKernelGGL((k_rtz_wide<1>), dim3(wgs), dim3(512), sm, s, a); break;
-        case 2: hipLaunchKernelGGL((k_rtz_wide<2>), dim3(wgs), dim3(512), sm, s, a); break;
-        case 3: hipLaunchKernelGGL((k_rtz_wide<3>), dim3(wgs), dim3(512), sm, s, a); break;
-        case 4: hipLaunchKernelGGL((k_rtz_wide<4>), dim3(wgs), dim3(512), sm, s, a); break;
-        case 5: hipLaunchKernelGGL((k_rtz_wide<5>), dim3(wgs), dim3(512), sm, s, a); break;
-        case 6: hipLaunchKernelGGL((k_rtz_wide<6>), dim3(wgs), dim3(512), sm, s, a); break;
-        case 7: hipLaunchKernelGGL((k_rtz_wide<7>), dim3(wgs), dim3(512), sm, s, a); break;
-        case 8: hipLaunchKernelGGL((k_rtz_wide<8>), dim3(wgs), dim3(512), sm, s, a); break;
-        case 9: hipLaunchKernelGGL((k_rtz_wide<9>), dim3(wgs), dim3(512), sm, s, a); break;
-        case 10: hipLaunchKernelGGL((k_rtz_wide<10>), dim3(wgs), dim3(512), sm, s, a); break;
-        case 11: hipLaunchKernelGGL((k_rtz_wide<11>), dim3(wgs), dim3(512), sm, s, a); break;
-        case 12: hipLaunchKernelGGL((k_rtz_wide<12>), dim3(wgs), dim3(512), sm, s, a); break;
-        default: hipLaunchKernelGGL((k_rtz_wide<13>), dim3(wgs), dim3(512), sm, s, a); break;
+        case 1: HMX_LAUNCH((k_rtz_wide<1>), dim3(wgs), dim3(512), sm, s, a); break;
+        case 2: HMX_LAUNCH((k_rtz_wide<2>), dim3(wgs), dim3(512), sm, s, a); break;
+        case 3: HMX_LAUNCH((k_rtz_wide<3>), dim3(wgs), dim3(512), sm, s, a); break;
+        case 4: HMX_LAUNCH((k_rtz_wide<4>), dim3(wgs), dim3(512), sm, s, a); break;
+        case 5: HMX_LAUNCH((k_rtz_wide<5>), dim3(wgs), dim3(512), sm, s, a); break;
+        case 6: HMX_LAUNCH((k_rtz_wide<6>), dim3(wgs), dim3(512), sm, s, a); break;
+        case 7: HMX_LAUNCH((k_rtz_wide<7>), dim3(wgs), dim3(512), sm, s, a); break;
+        case 8: HMX_LAUNCH((k_rtz_wide<8>), dim3(wgs), dim3(512), sm, s, a); break;
+        case 9: HMX_LAUNCH((k_rtz_wide<9>), dim3(wgs), dim3(512), sm, s, a); break;
+        case 10: HMX_LAUNCH((k_rtz_wide<10>), dim3(wgs), dim3(512), sm, s, a); break;
+        case 11: HMX_LAUNCH((k_rtz_wide<11>), dim3(wgs), dim3(512), sm, s, a); break;
+        case 12: HMX_LAUNCH((k_rtz_wide<12>), dim3(wgs), dim3(512), sm, s, a); break;
+        default: HMX_LAUNCH((k_rtz_wide<13>), dim3(wgs), dim3(512), sm, s, a); break;
     }
 }
 
@@ -5008,7 +5008,7 @@ void launch_rtz_wide_reduce(const float* slab, int nslabs, int mt, int dp, int K
                             hipStream_t s) {
     const int ntd = dp / 16;
     const int seg_len = 8;
-    hipLaunchKernelGGL(k_rtz2_reduce, dim3(cdiv(mt * ntd * 256, 256), cdiv(nslabs, seg_len)), dim3(256), 0, s, slab, nslabs, mt,
+    HMX_LAUNCH(k_rtz2_reduce, dim3(cdiv(mt * ntd * 256, 256), cdiv(nslabs, seg_len)), dim3(256), 0, s, slab, nslabs, mt,
                        ntd, K16, ld, out, task_grp, seg_len);
 }
 
@@ -5021,7 +5021,7 @@ void rtz_geometry(int mt, int ntd, int* nsub, int* slab_per_wave) {
 void launch_rtz(const RtzArgs& a, int wgs, hipStream_t s) {
     int nsub, spw;
     rtz_geometry(a.mt, a.ntd, &nsub, &spw);
-    hipLaunchKernelGGL((k_rtz<HMX_RTZ_MTW, HMX_RTZ_NTW>), dim3(wgs, nsub), dim3(256), 0, s, a);
+    HMX_LAUNCH((k_rtz<HMX_RTZ_MTW, HMX_RTZ_NTW>), dim3(wgs, nsub), dim3(256), 0, s, a);
 }
 
 void launch_rtz_reduce(const float* slab, int nwaves, int mt, int ntd, int K16, int ld, double* out,
@@ -5029,80 +5029,80 @@ void launch_rtz_reduce(const float* slab, int nwaves, int mt, int ntd, int K16, 
     int nsub, spw;
     rtz_geometry(mt, ntd, &nsub, &spw);
     const int seg_len = 32;   // slabs summed by one thread before its fp64 atomic
-    hipLaunchKernelGGL((k_rtz_reduce<HMX_RTZ_MTW, HMX_RTZ_NTW>), dim3(cdiv(spw, 256), cdiv(nwaves, seg_len)), dim3(256), 0, s,
+    HMX_LAUNCH((k_rtz_reduce<HMX_RTZ_MTW, HMX_RTZ_NTW>), dim3(cdiv(spw, 256), cdiv(nwaves, seg_len)), dim3(256), 0, s,
                        slab, nwaves, nsub, ntd, K16, ld, out, task_grp, seg_len);
 }
 
 void launch_block_table(const TableArgs& a, int K16, hipStream_t s) {
     const size_t sm = (size_t)a.B * 8 + 128 * 8 + (size_t)a.B * 4 + 16;
-    hipLaunchKernelGGL(k_block_table, dim3(K16), dim3(128), sm, s, a);
+    HMX_LAUNCH(k_block_table, dim3(K16), dim3(128), sm, s, a);
 }
 
 void launch_group_sums(const float* R, int Kp, int K, int K16, const int* cells, const int* tile_grp, int n_tiles,
                        double* Ogrp, hipStream_t s) {
     if (n_tiles <= 0) return;
-    hipLaunchKernelGGL(k_group_sums, dim3(n_tiles), dim3(128), 0, s, R, Kp, K, K16, cells, tile_grp, n_tiles, Ogrp);
+    HMX_LAUNCH(k_group_sums, dim3(n_tiles), dim3(128), 0, s, R, Kp, K, K16, cells, tile_grp, n_tiles, Ogrp);
 }
 
 void launch_ridge_solve(const RidgeSolveArgs& a, hipStream_t s) {
-    if (a.V == 1) hipLaunchKernelGGL(k_ridge_solve_v1, dim3(a.K16), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL(k_ridge_solve_general, dim3(a.K16), dim3(256), 0, s, a);
+    if (a.V == 1) HMX_LAUNCH(k_ridge_solve_v1, dim3(a.K16), dim3(64), 0, s, a);
+    else HMX_LAUNCH(k_ridge_solve_general, dim3(a.K16), dim3(256), 0, s, a);
 }
 
 void launch_order(const OrderArgs& a, hipStream_t s) {
     const int nchunks = cdiv(a.N, ORDER_CHUNK);
     const size_t sm = (size_t)a.nblk * a.G * sizeof(int);
-    hipLaunchKernelGGL(k_order_pass<0>, dim3(nchunks), dim3(64), sm, s, a);
-    hipLaunchKernelGGL(k_order_scan, dim3(a.nblk * a.G), dim3(256), 0, s, a, nchunks);
-    hipLaunchKernelGGL(k_order_runs, dim3(a.nblk * a.G), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_order_pass<1>, dim3(nchunks), dim3(64), sm, s, a);
+    HMX_LAUNCH(k_order_pass<0>, dim3(nchunks), dim3(64), sm, s, a);
+    HMX_LAUNCH(k_order_scan, dim3(a.nblk * a.G), dim3(256), 0, s, a, nchunks);
+    HMX_LAUNCH(k_order_runs, dim3(a.nblk * a.G), dim3(256), 0, s, a);
+    HMX_LAUNCH(k_order_pass<1>, dim3(nchunks), dim3(64), sm, s, a);
 }
 
 int order_chunks(int64_t N) { return cdiv(N, ORDER_CHUNK); }
 
 void launch_gather_rows(const float* src, int ld, int cols, const int* rows, int n_rows, float* dst, hipStream_t s) {
     if (n_rows <= 0) return;
-    hipLaunchKernelGGL(k_gather_rows, dim3(cdiv((int64_t)n_rows * cols, 256)), dim3(256), 0, s, src, ld, cols, rows, n_rows, dst);
+    HMX_LAUNCH(k_gather_rows, dim3(cdiv((int64_t)n_rows * cols, 256)), dim3(256), 0, s, src, ld, cols, rows, n_rows, dst);
 }
 
 template <int MTD>
 static void launch_apply2_k(const ApplyArgs& a, int kb, size_t sm, hipStream_t s) {
     switch (kb) {
-        case 1: hipLaunchKernelGGL((k_ridge_apply2<MTD, 1>), dim3(a.ntasks), dim3(256), sm, s, a); break;
-        case 2: hipLaunchKernelGGL((k_ridge_apply2<MTD, 2>), dim3(a.ntasks), dim3(256), sm, s, a); break;
-        case 3: hipLaunchKernelGGL((k_ridge_apply2<MTD, 3>), dim3(a.ntasks), dim3(256), sm, s, a); break;
-        case 4: hipLaunchKernelGGL((k_ridge_apply2<MTD, 4>), dim3(a.ntasks), dim3(256), sm, s, a); break;
-        case 5: hipLaunchKernelGGL((k_ridge_apply2<MTD, 5>), dim3(a.ntasks), dim3(256), sm, s, a); break;
-        case 6: hipLaunchKernelGGL((k_ridge_apply2<MTD, 6>), dim3(a.ntasks), dim3(256), sm, s, a); break;
-        default: hipLaunchKernelGGL((k_ridge_apply2<MTD, 7>), dim3(a.ntasks), dim3(256), sm, s, a); break;
+        case 1: HMX_LAUNCH((k_ridge_apply2<MTD, 1>), dim3(a.ntasks), dim3(256), sm, s, a); break;
+        case 2: HMX_LAUNCH((k_ridge_apply2<MTD, 2>), dim3(a.ntasks), dim3(256), sm, s, a); break;
+        case 3: HMX_LAUNCH((k_ridge_apply2<MTD, 3>), dim3(a.ntasks), dim3(256), sm, s, a); break;
+        case 4: HMX_LAUNCH((k_ridge_apply2<MTD, 4>), dim3(a.ntasks), dim3(256), sm, s, a); break;
+        case 5: HMX_LAUNCH((k_ridge_apply2<MTD, 5>), dim3(a.ntasks), dim3(256), sm, s, a); break;
+        case 6: HMX_LAUNCH((k_ridge_apply2<MTD, 6>), dim3(a.ntasks), dim3(256), sm, s, a); break;
+        default: HMX_LAUNCH((k_ridge_apply2<MTD, 7>), dim3(a.ntasks), dim3(256), sm, s, a); break;
     }
 }
 
 void launch_load_rows(const float* src, int d, const int* source_row, float* dst, int dp, int64_t N, hipStream_t s) {
     if (N <= 0) return;
-    hipLaunchKernelGGL(k_load_rows, dim3(cdiv(N * dp, 256)), dim3(256), 0, s, src, d, source_row, dst, dp, N);
+    HMX_LAUNCH(k_load_rows, dim3(cdiv(N * dp, 256)), dim3(256), 0, s, src, d, source_row, dst, dp, N);
 }
 
 void launch_kmeans_seed(const SeedArgs& a, int K, hipStream_t s) {
     const int wgs = cdiv(a.n, 256);
-    hipLaunchKernelGGL(k_seed_transpose, dim3(cdiv((int64_t)a.n * a.d, 256)), dim3(256), 0, s, a.X, a.n, a.d, a.Xt);
+    HMX_LAUNCH(k_seed_transpose, dim3(cdiv((int64_t)a.n * a.d, 256)), dim3(256), 0, s, a.X, a.n, a.d, a.Xt);
     const size_t sm = (size_t)SEED_TRIALS * a.d * sizeof(float);
     for (int step = 0; step < K; ++step) {
-        hipLaunchKernelGGL(k_seed_pick, dim3(1), dim3(256), 0, s, a, step);
-        hipLaunchKernelGGL(k_seed_eval, dim3(wgs), dim3(256), sm, s, a, step);
-        hipLaunchKernelGGL(k_seed_commit, dim3(wgs), dim3(256), 0, s, a, step);
+        HMX_LAUNCH(k_seed_pick, dim3(1), dim3(256), 0, s, a, step);
+        HMX_LAUNCH(k_seed_eval, dim3(wgs), dim3(256), sm, s, a, step);
+        HMX_LAUNCH(k_seed_commit, dim3(wgs), dim3(256), 0, s, a, step);
     }
 }
 
 size_t y_planes_dwords(int K16, int dp) { return (size_t)((dp + 31) / 32) * 3 * (K16 / 16) * 256; }
 void launch_y_planes(const float* Y, int K16, int ldy, int dp, unsigned* Yf, hipStream_t s) {
     const int ns = (dp + 31) / 32, mt = K16 / 16;
-    hipLaunchKernelGGL(k_y_planes, dim3(ns * mt), dim3(64), 0, s, Y, ldy, mt, Yf);
+    HMX_LAUNCH(k_y_planes, dim3(ns * mt), dim3(64), 0, s, Y, ldy, mt, Yf);
 }
 size_t w_planes_dwords(int G, int K16, int dp) { return (size_t)G * ((K16 + 31) / 32) * 3 * (dp / 16) * 256; }
 void launch_w_planes(const float* W, int G, int K16, int ldw, int dp, unsigned* Wf, hipStream_t s) {
     const int ns = (K16 + 31) / 32, mtd = dp / 16;
-    hipLaunchKernelGGL(k_w_planes, dim3(ns * mtd, G), dim3(64), 0, s, W, K16, ldw, mtd, ns, Wf);
+    HMX_LAUNCH(k_w_planes, dim3(ns * mtd, G), dim3(64), 0, s, W, K16, ldw, mtd, ns, Wf);
 }
 
 int launch_ridge_apply(const ApplyArgs& a_in, int max_wgs, hipStream_t s) {
@@ -5118,7 +5118,7 @@ int launch_ridge_apply(const ApplyArgs& a_in, int max_wgs, hipStream_t s) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_ridge_apply_wideb<M>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); \
             attr_done = true;                                                                                         \
         }                                                                                                             \
-        hipLaunchKernelGGL((k_ridge_apply_wideb<M>), dim3(a.ntasks), dim3(64 * APPLYB_WAVES), sm, s, a);               \
+        HMX_LAUNCH((k_ridge_apply_wideb<M>), dim3(a.ntasks), dim3(64 * APPLYB_WAVES), sm, s, a);               \
     } break;
         if (mtd < 1 || mtd > 13 || sm > (size_t)80 * 1024) return -1;   // (13 column tiles: 78 KB, the attribute's 80 KB)
         switch (mtd) {
@@ -5132,10 +5132,10 @@ int launch_ridge_apply(const ApplyArgs& a_in, int max_wgs, hipStream_t s) {
         const int mtd = a.dp / 16;
         a.ldw_lds = ((16 * mtd + 31) / 32) * 32 + 16;
         const size_t sm = (size_t)2 * 16 * a.ldw_lds * sizeof(float);
-#define HMX_AW(M) case M: hipLaunchKernelGGL((k_ridge_apply_wide<M>), dim3(a.ntasks), dim3(64 * WIDE_WAVES), sm, s, a); break;
+#define HMX_AW(M) case M: HMX_LAUNCH((k_ridge_apply_wide<M>), dim3(a.ntasks), dim3(64 * WIDE_WAVES), sm, s, a); break;
         switch (mtd) {
             HMX_AW(1) HMX_AW(2) HMX_AW(3) HMX_AW(4) HMX_AW(5) HMX_AW(6) HMX_AW(7) HMX_AW(8) HMX_AW(9) HMX_AW(10) HMX_AW(11) HMX_AW(12)
-            default: hipLaunchKernelGGL((k_ridge_apply_wide<13>), dim3(a.ntasks), dim3(64 * WIDE_WAVES), sm, s, a); break;
+            default: HMX_LAUNCH((k_ridge_apply_wide<13>), dim3(a.ntasks), dim3(64 * WIDE_WAVES), sm, s, a); break;
         }
 #undef HMX_AW
         return 0;
@@ -5150,9 +5150,9 @@ int launch_ridge_apply(const ApplyArgs& a_in, int max_wgs, hipStream_t s) {
     }
     constexpr int NT = 2;
     const int wgs = assign_grid(a.n_tiles, NT, max_wgs);
-    if (a.mtd <= 4) hipLaunchKernelGGL((k_ridge_apply<4, NT>), dim3(wgs), dim3(256), 0, s, a);
-    else if (a.mtd <= 13) hipLaunchKernelGGL((k_ridge_apply<13, NT>), dim3(wgs), dim3(256), 0, s, a);
-    else if (a.mtd <= 20) hipLaunchKernelGGL((k_ridge_apply<20, 1>), dim3(assign_grid(a.n_tiles, 1, max_wgs)), dim3(256), 0, s, a);   // up to 320 PCs
+    if (a.mtd <= 4) HMX_LAUNCH((k_ridge_apply<4, NT>), dim3(wgs), dim3(256), 0, s, a);
+    else if (a.mtd <= 13) HMX_LAUNCH((k_ridge_apply<13, NT>), dim3(wgs), dim3(256), 0, s, a);
+    else if (a.mtd <= 20) HMX_LAUNCH((k_ridge_apply<20, 1>), dim3(assign_grid(a.n_tiles, 1, max_wgs)), dim3(256), 0, s, a);   // up to 320 PCs
     else return -1;
     return 0;
 }

@@ -1171,7 +1171,7 @@ static void launch_rtz3_t(const Rtz3Args& a, size_t sm, hipStream_t s) {
     if (!prof) (void)hipMalloc(reinterpret_cast<void**>(&prof), (size_t)4096 * RTZ3_WAVES * 8 * 8);
     (void)hipMemsetAsync(prof, 0, (size_t)a.ntasks * RTZ3_WAVES * 8 * 8, s);
     b.prof = prof;
-    hipLaunchKernelGGL((k_rtz3<MT, KS, NTB>), dim3(a.ntasks), dim3(64 * RTZ3_WAVES), sm, s, b);
+    HMX_LAUNCH((k_rtz3<MT, KS, NTB>), dim3(a.ntasks), dim3(64 * RTZ3_WAVES), sm, s, b);
     if (++calls == 30) {
         std::vector<unsigned long long> h((size_t)a.ntasks * RTZ3_WAVES * 8);
         (void)hipStreamSynchronize(s);
@@ -1190,7 +1190,7 @@ static void launch_rtz3_t(const Rtz3Args& a, size_t sm, hipStream_t s) {
     }
     return;
 #endif
-    hipLaunchKernelGGL((k_rtz3<MT, KS, NTB>), dim3(a.ntasks), dim3(64 * RTZ3_WAVES), sm, s, a);
+    HMX_LAUNCH((k_rtz3<MT, KS, NTB>), dim3(a.ntasks), dim3(64 * RTZ3_WAVES), sm, s, a);
 }
 template <int KS, int NTB>
 static void launch_rtz3_m(const Rtz3Args& a, int mt, size_t sm, hipStream_t s) {
@@ -1228,7 +1228,7 @@ static void launch_rtz3c_t(const Rtz3Args& a, size_t sm, hipStream_t s) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_rtz3c<MT, KS, NTB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_done = true;
     }
-    hipLaunchKernelGGL((k_rtz3c<MT, KS, NTB>), dim3(a.ntasks), dim3(64 * RTZ3C_WAVES), sm, s, a);
+    HMX_LAUNCH((k_rtz3c<MT, KS, NTB>), dim3(a.ntasks), dim3(64 * RTZ3C_WAVES), sm, s, a);
 }
 template <int KS, int NTB>
 static void launch_rtz3c_m(const Rtz3Args& a, int mt, size_t sm, hipStream_t s) {
@@ -1277,7 +1277,7 @@ void launch_rtz3_finish(const Rtz3FinishArgs& a, hipStream_t s) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_rtz3_finish), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_done = true;
     }
-    hipLaunchKernelGGL(k_rtz3_finish, dim3(a.K16), dim3(RTZ3_FIN_THREADS), sm, s, a);
+    HMX_LAUNCH(k_rtz3_finish, dim3(a.K16), dim3(RTZ3_FIN_THREADS), sm, s, a);
 }
 
 // ---- wide shapes (k_rtzw)
@@ -1302,7 +1302,7 @@ static void launch_rtzw_t(const Rtz3Args& a, size_t sm, hipStream_t s) {
     if (!prof) (void)hipMalloc(reinterpret_cast<void**>(&prof), (size_t)4096 * 8 * 8 * 8);
     (void)hipMemsetAsync(prof, 0, (size_t)a.ntasks * 8 * 8 * 8, s);
     b.prof = prof;
-    hipLaunchKernelGGL((k_rtzw<MT>), dim3(a.ntasks), dim3(64 * RTZW_WAVES), sm, s, b);
+    HMX_LAUNCH((k_rtzw<MT>), dim3(a.ntasks), dim3(64 * RTZW_WAVES), sm, s, b);
     if (++calls == 12) {
         std::vector<unsigned long long> h((size_t)a.ntasks * 8 * 8);
         (void)hipStreamSynchronize(s);
@@ -1318,7 +1318,7 @@ static void launch_rtzw_t(const Rtz3Args& a, size_t sm, hipStream_t s) {
     }
     return;
 #endif
-    hipLaunchKernelGGL((k_rtzw<MT>), dim3(a.ntasks), dim3(64 * RTZW_WAVES), sm, s, a);
+    HMX_LAUNCH((k_rtzw<MT>), dim3(a.ntasks), dim3(64 * RTZW_WAVES), sm, s, a);
 }
 
 // ---- Z_cos as bf16 planes in k_rtzw2b's B-fragment order (see the kernel): one 512-byte piece per (static tile, column tile, plane)
@@ -1356,7 +1356,7 @@ __global__ __launch_bounds__(256) void k_zplanes(const float* __restrict__ Z, in
 }
 void launch_zplanes(const float* Z, int dp, int n_tiles, const int* tile_grp, const int* gstart, const int* s_tile_start, unsigned* Zf, hipStream_t s) {
     if (n_tiles <= 0) return;
-    hipLaunchKernelGGL(k_zplanes, dim3(std::min(n_tiles, 256 * 16)), dim3(256), 0, s, Z, dp, n_tiles, tile_grp, gstart, s_tile_start, Zf);
+    HMX_LAUNCH(k_zplanes, dim3(std::min(n_tiles, 256 * 16)), dim3(256), 0, s, Z, dp, n_tiles, tile_grp, gstart, s_tile_start, Zf);
 }
 
 // ---- k_rtzw2b: K > 112, seven to fourteen column tiles; four tile buffers in one CU's LDS
@@ -1372,7 +1372,7 @@ static void launch_rtzw2b_z(const Rtz3Args& a, size_t sm, hipStream_t s) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_rtzw2b<MT, NTH, ZF>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_done = true;
     }
-    hipLaunchKernelGGL((k_rtzw2b<MT, NTH, ZF>), dim3(a.ntasks), dim3(64 * RTZWB_WAVES), sm, s, a);
+    HMX_LAUNCH((k_rtzw2b<MT, NTH, ZF>), dim3(a.ntasks), dim3(64 * RTZWB_WAVES), sm, s, a);
 }
 template <int MT, int NTH>
 static void launch_rtzw2b_t(const Rtz3Args& a, size_t sm, hipStream_t s) {
@@ -1426,5 +1426,5 @@ int launch_rtzw(const Rtz3Args& a_in, int mt, int dp, int d, int nblk, hipStream
 void launch_tile_blocks(const int* cells, const int* tile_grp, const int* blk_start, int nblk, int64_t n_pos_upper, const int* gstart,
                         const int* s_tile_start, unsigned char* tile_blk, hipStream_t s) {
     const int wgs = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (n_pos_upper + 1023) / 1024));
-    hipLaunchKernelGGL(k_tile_blocks, dim3(wgs), dim3(256), 0, s, cells, tile_grp, blk_start, nblk, gstart, s_tile_start, tile_blk);
+    HMX_LAUNCH(k_tile_blocks, dim3(wgs), dim3(256), 0, s, cells, tile_grp, blk_start, nblk, gstart, s_tile_start, tile_blk);
 }

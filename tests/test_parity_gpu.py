@@ -327,18 +327,7 @@ def test_config2_shape_properties_and_oracle():
     np.testing.assert_allclose(np.linalg.norm(ho.Y, axis=0), 1.0, atol=3e-6)
 
 
-def _device_perm_source(N, seed):
-    """The engine's device-side update order as the permutation stream the oracle consumes
-    (harmony.py:471): position p of round r holds the cell whose keyed-bijection position is p."""
-    from oracle.device_order import positions
-    state = {"counter": 0}
-
-    def perm(n):
-        assert n == N
-        pos = positions(np.arange(N), N, seed, state["counter"])
-        state["counter"] += 1
-        return np.argsort(pos, kind="stable")
-    return perm
+from step_reference import device_perm_source as _device_perm_source  # noqa: E402  (shared with tests/test_instance_grid_gpu.py)
 
 
 def _bench_path_case(N, d, B, K, monkeypatch, ridge_dtype, rounds=(5, 5)):
@@ -1008,12 +997,15 @@ def test_device_order_gives_equivalent_correction(monkeypatch):
 # ------------------------------------------------------------------------------------------
 # device-side Lloyd iterations of the initial k-means (hmx_kmeans_lloyd)
 # ------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("N,d,K", [(5000, 20, 12), (3333, 50, 100), (700, 7, 3), (2500, 80, 120), (1500, 30, 150), (4000, 200, 200)])
+@pytest.mark.parametrize("N,d,K", [(5000, 20, 12), (3333, 50, 100), (700, 7, 3), (2500, 80, 120), (1500, 30, 150), (4000, 200, 200),
+                                   (3000, 25, 24), (3000, 40, 40), (3000, 29, 56), (3500, 61, 72), (3500, 47, 88)])
 def test_device_lloyd_matches_numpy_lloyd(N, d, K, monkeypatch):
     """Same seeds, same number of iterations: the GPU's Euclidean Lloyd iterations over Z_cos give
     the centres of a plain NumPy restatement (argmax of z.c - |c|^2/2, mean of the members) -- the narrow shapes on
-    k_kmeans_step, K > 112 or d > 64 (BASELINE configs[4]'s regime) through the one-hot R and the streaming R^T.Z pass."""
-    from harmonypy_amd import harmony as H
+    k_kmeans_step (every instance: 1..7 cluster tiles, named by the launch census), K > 112 or d > 64 (BASELINE configs[4]'s
+    regime) through the one-hot R and the streaming R^T.Z pass."""
+    from harmonypy_amd import _capi, harmony as H
+    from instance_grid import instance_name
     rng = np.random.default_rng(K)
     cent = rng.normal(size=(K, d)) * 4.0
     lab = rng.integers(0, K, size=N)
@@ -1030,8 +1022,12 @@ def test_device_lloyd_matches_numpy_lloyd(N, d, K, monkeypatch):
             m = labels == k
             if m.any():
                 C[k] = Zc[m].mean(axis=0)
+    _capi.launch_census(True)
     got = ho._engine.kmeans_lloyd(C0, 6)
+    launched = {instance_name(n) for n in _capi.launch_census(False)}
     assert got.shape == (K, d) and np.isfinite(got).all()
+    if K <= 112 and d <= 64:
+        assert f"k_kmeans_step<{(K + 15) // 16}>" in launched, sorted(x for x in launched if x)
     # a handful of boundary cells may fall on the other side in fp32: compare centre by centre, loosely
     err = np.abs(got - C).max(axis=1)
     assert np.median(err) < 1e-5 and (err < 5e-3).mean() > 0.9, (np.median(err), err.max())
